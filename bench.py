@@ -18,6 +18,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with two extra o
                  during the timed region (rocm-smi) and inside the GEMM launches (the kernel's own cycle / real-time stamps),
                  the fraction against the peak at that clock, per-class times, the committed in-pipeline PMC summary
   cpu_baseline - the oracle (PyTorch-CPU restatement of the reference path) timed on this host
+
+--dump-outputs DIR: rank 0 also writes what the last timed step returned as DIR/<name>.npy (see its help text).
 """
 import argparse
 import json
@@ -30,7 +32,7 @@ import torch
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from benchlib import ClockSampler, bind_rank_to_numa, hbm_classes, host_cpu_info, pmc_in_run  # noqa: E402  (untimed measurement helpers)
+from benchlib import ClockSampler, bind_rank_to_numa, dump_outputs, hbm_classes, host_cpu_info, pmc_in_run  # noqa: E402  (untimed measurement helpers)
 
 PEAK_BF16_TFLOPS = 2500.0   # MI355X dense bf16 MFMA peak, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_F32_MFMA_TFLOPS = 157.3   # fp32-input MFMA (= the fp32 vector peak), same guide: --precision fp32 runs are priced against it
@@ -69,6 +71,11 @@ def parse(extra=None):
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the in-run rocprofv3 --pmc passes (fabric traffic, matrix-pipe busy): roofline.traffic / "
                          "pmc_in_pipeline then come from the committed profiles/ files, flagged measured_in_run: false")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the LAST timed step returned to its caller as DIR/<name>.npy "
+                         "(attack: x_adv; train: the entries of train_step's dict), float32 / float64, below 64 MB in all - a larger "
+                         "array as a fixed seeded sample of its elements (benchlib.dump_outputs).  Inputs and weights are seeded, "
+                         "so the same arguments give the same files on any build that computes the same thing")
     if extra is not None:
         extra.add_arguments(ap)
     args = ap.parse_args()
@@ -184,6 +191,8 @@ def bench_train(args, R, cfg, sd, dev, dist, world, rank, coll_dev=None, rehears
         out = tr.train_step(x, None, global_batch=world * B)
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     if dist is not None:
         t = torch.tensor([el], device=coll_dev if coll_dev is not None else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -341,6 +350,8 @@ def main(extra=None):
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
+    if args.dump_outputs and rank == 0:            # before the untimed extra calls below run the same step again
+        dump_outputs(args.dump_outputs, {"x_adv": out})
     # Every rank then looks at its OWN GPU (untimed extra calls, all ranks at once so that the node is loaded as in the timed
     # region): rocm-smi clock / socket power of its device and the shader clock its GEMM launches actually got.  The boxes of this
     # pool hold 1.74-1.92 GHz under the power cap; a 1 -> 8 curve has to show whether a slow rank is a slow GPU.

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Measurement helpers of bench.py that are NOT part of the timed region (moved out of bench.py in round 6 so that the
 headline harness reads top to bottom): host description, the HBM-class roofline objects, the in-run rocprofv3 PMC passes,
-the rocm-smi clock / power sampler and the NUMA binding of a rank.  Nothing here touches the oracle or the timed loop."""
+the rocm-smi clock / power sampler, the NUMA binding of a rank and the --dump-outputs writer.  Nothing here touches the oracle
+or the timed loop."""
 import os
 import sys
 import time
@@ -30,6 +31,32 @@ def host_cpu_info():
     except OSError:
         pass
     return model, (len(cores) or (os.cpu_count() or 1)), os.cpu_count() or 1
+
+
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: array data written by one run; the files (.npy headers included) stay below 64 MB
+
+
+def dump_outputs(directory: str, outputs: dict, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """--dump-outputs: what the last timed call returned to its caller, one `<directory>/<name>.npy` per entry of `outputs`
+    (tensors or Python numbers; None entries are left out).  float64 stays float64, every other dtype is written as float32.
+    At most `budget` bytes of array data in all: an array above its equal share of the budget is written as a 1-D sample of
+    its flattened elements at ascending indices drawn (with repetition) by numpy's default_rng(0) from (elements, sample
+    size) alone, so two runs with the same arguments - or two builds of the project - write the same positions.
+    Returns {name: elements written}."""
+    import numpy as np
+    arrays = {k: torch.as_tensor(v).detach() for k, v in outputs.items() if v is not None}
+    os.makedirs(directory, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    written = {}
+    for name, t in arrays.items():
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        keep = share // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), size=keep))
+            t = t.flatten()[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(directory, f"{name}.npy"), t.cpu().numpy())
+        written[name] = t.numel()
+    return written
 
 
 PEAK_HBM_TBPS = 8.0         # MI355X HBM3E peak, /opt/skills/guides/MI355X_MICROARCH.md (6.3 TB/s achievable)

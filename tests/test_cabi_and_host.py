@@ -197,6 +197,39 @@ def test_bench_host_helpers():
     assert b.bind_rank_to_numa(0, 1) is None
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: one .npy per returned value, float32 / float64 only, a fixed sample once the budget is exceeded."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    g = torch.Generator().manual_seed(0)
+    x = torch.rand(2, 3, 4, 4, generator=g)
+    out = {"x_adv": x, "loss": torch.tensor(1.5, dtype=torch.float64), "lr": 1e-3, "acc": None,
+           "h": torch.randn(5, 7, generator=g).bfloat16(), "y": torch.arange(6)}
+    d = tmp_path / "small" / "nested"                       # the directory is created
+    assert b.dump_outputs(str(d), out) == {"x_adv": 96, "loss": 1, "lr": 1, "h": 35, "y": 6}
+    assert sorted(p.name for p in d.iterdir()) == ["h.npy", "loss.npy", "lr.npy", "x_adv.npy", "y.npy"]
+    got = {p.stem: np.load(p) for p in d.iterdir()}
+    assert got["x_adv"].dtype == np.float32 and np.array_equal(got["x_adv"], x.numpy())
+    assert got["loss"].dtype == np.float64 and got["loss"].shape == () and got["loss"] == 1.5
+    assert got["lr"].dtype == np.float32 and got["lr"] == np.float32(1e-3)
+    assert got["h"].dtype == np.float32 and np.array_equal(got["h"], out["h"].float().numpy())
+    assert got["y"].dtype == np.float32 and np.array_equal(got["y"], np.arange(6, dtype=np.float32))
+    # over the budget: every array gets an equal share, the large one is cut to a seeded sample of its flattened elements
+    big = torch.rand(100, 100, generator=g)
+    for run in ("a", "b"):
+        assert b.dump_outputs(str(tmp_path / run), {"big": big, "small": x}, budget=4096) == {"big": 512, "small": 96}
+    a, a2 = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    idx = np.sort(np.random.default_rng(0).integers(0, big.numel(), size=512))
+    assert a.shape == (512,) and np.array_equal(a, big.flatten().numpy()[idx]) and np.array_equal(a, a2)
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), x.numpy())
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / "a").iterdir()) <= 4096
+    import benchlib                                         # scripts/ is on sys.path once bench.py is loaded
+    assert benchlib.DUMP_BUDGET_BYTES + 128 * 64 < 64e6            # the shipped budget: below 64 MB on disk, headers included
+
+
 def test_checkpoint_layout_and_formats(tmp_path):
     """File names / cadence of …clip.py:239-244,467-479 and the two on-disk model formats."""
     import torch

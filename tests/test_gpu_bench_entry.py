@@ -123,6 +123,33 @@ def test_two_rank_rehearsal_train_step_line():
     assert d["final_loss"] == d["final_loss"]        # finite
 
 
+def test_dump_outputs_same_arguments_same_files(tmp_path):
+    """--dump-outputs DIR: what the last timed pgd() call returned (x_adv) as float32, bit for bit the same from two runs with
+    the same arguments - inputs and weights are seeded - and the JSON line unchanged by the option."""
+    import numpy as np
+    got = []
+    for name in ("a", "b"):
+        d = _one_line(run("--gpus", "1", *SMALL, "--no-roofline", "--dump-outputs", str(tmp_path / name)))
+        assert d["steps"] == 2 and d["value"] > 0
+        assert os.listdir(tmp_path / name) == ["x_adv.npy"]
+        got.append(np.load(tmp_path / name / "x_adv.npy"))
+    a, b = got
+    assert a.dtype == np.float32 and a.shape == (8, 3, 224, 224)
+    assert np.isfinite(a).all() and a.min() >= 0 and a.max() <= 1 and a.std() > 0.1
+    assert np.array_equal(a, b)
+
+
+def test_dump_outputs_train_step(tmp_path):
+    """--mode train --dump-outputs: the entries of the dict the last timed train_step returned, one scalar file each."""
+    import numpy as np
+    d = _one_line(run("--gpus", "1", "--mode", "train", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "4",
+                      "--iterations", "2", "--dump-outputs", str(tmp_path)))
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert sorted(got) == ["cos_sim", "cos_sim_clean", "loss", "loss_clean", "loss_total", "lr"]     # acc / racc are None: no labels
+    assert all(v.dtype == np.float32 and v.size == 1 and np.isfinite(v).all() for v in got.values())
+    assert abs(float(got["loss"]) - d["final_loss"]) <= 1e-6 * abs(d["final_loss"])
+
+
 def test_fp32_line_is_priced_against_the_fp32_matrix_peak():
     """--precision fp32 (the reference's own precision on v_mfma_f32_32x32x2_f32): dtype, roofline peak and kernel name of the line."""
     d = _one_line(run("--gpus", "1", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "8", "--precision", "fp32",
