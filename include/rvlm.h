@@ -26,6 +26,9 @@ extern "C" {
 #endif
 
 #define RVLM_VERSION 109
+/* Additions made without a version step are announced by a feature macro (a binding can also probe the symbol):
+ * RVLM_HAS_TEXT: the rvlm_text_* entry points and RVLM_FLAG_TOKEN_RANGE / RVLM_FLAG_EOT_ACTIVE */
+#define RVLM_HAS_TEXT 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -53,7 +56,10 @@ enum {
     RVLM_FLAG_INPUT_RANGE = 1, /* data_clean outside [0,1] (+-1e-6)          pgd_train.py:24    */
     RVLM_FLAG_NAN_GRAD = 2,    /* NaN in the gradient (zeroed, not an error) pgd_train.py:40-42 */
     RVLM_FLAG_NAN_DELTA = 4,   /* NaN in the perturbation                    pgd_train.py:60    */
-    RVLM_FLAG_ADV_RANGE = 8    /* x+delta left [0,1] (+-1e-6)                pgd_train.py:61-63 */
+    RVLM_FLAG_ADV_RANGE = 8,   /* x+delta left [0,1] (+-1e-6)                pgd_train.py:61-63 */
+    /* rvlm_text_encode (RVLM_HAS_TEXT); where the reference would fault inside nn.Embedding or pool the wrong row */
+    RVLM_FLAG_TOKEN_RANGE = 16, /* a token id outside [0, vocab)                                  */
+    RVLM_FLAG_EOT_ACTIVE = 32   /* a prompt's EOT position (argmax of its ids) is >= active_len   */
 };
 
 /* ---------------------------------------------------------------------------------------------
@@ -383,6 +389,47 @@ int rvlm_comm_info(const rvlm_comm* comm, int* rank, int* world);
 int rvlm_allreduce_grads(rvlm_comm* comm, void* buf, size_t count, int dtype, rvlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Text tower: open_clip CLIP.encode_text, forward only (RVLM_HAS_TEXT).  Builds the zero-shot / TeCoA head
+ * embedding_text_labels_norm = encode_text(tokenize(prompts), normalize=True).T that the reference
+ * computes under no_grad on the frozen model (train/adversarial_training_clip.py:150-180,
+ * CLIP_eval/eval_utils.py:63-85, 80-template ensemble CLIP_eval/clip_robustbench.py:186-224).
+ * Tokenisation stays with the caller: tokens are what open_clip.tokenize returns.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rvlm_text rvlm_text;
+typedef struct {
+    int32_t vocab;     /* 49408 */
+    int32_t context;   /* 77 (<= 96) */
+    int32_t width;     /* = heads * 64 */
+    int32_t layers;
+    int32_t heads;
+    int32_t out_dim;   /* multiple of 4 */
+    int32_t act;       /* RVLM_ACT_* (QuickGELU for OpenAI weights) */
+    int32_t precision; /* RVLM_PREC_* */
+    int32_t max_batch; /* prompts per call; 0 -> 1024 */
+} rvlm_text_config;
+typedef struct {
+    const float* token_embedding;      /* [vocab, W]   */
+    const float* positional_embedding; /* [context, W] */
+    const float* ln_final_weight;      /* [W] */
+    const float* ln_final_bias;
+    const float* text_projection;      /* [W, out_dim] */
+    const rvlm_vit_block_weights* blocks_host; /* HOST array of `layers` structs of device ptrs: the vision tower's block layout */
+} rvlm_text_weights;
+/* model_orig = open_clip.create_model_and_transforms(...) (train/adversarial_training_clip.py:95-97): copies / converts the text
+ * weights, allocates the workspace.  RVLM_ERR_UNSUPPORTED for RVLM_PREC_F32X3 with a max_batch whose fc2 split operand would pass
+ * 2^31 bytes (about 1 500 prompts at width 768). */
+int rvlm_text_create(const rvlm_text_config* cfg, const rvlm_text_weights* weights, rvlm_stream_t stream, rvlm_text** out);
+int rvlm_text_destroy(rvlm_text* h);
+size_t rvlm_text_workspace_bytes(const rvlm_text* h);
+/* out_emb[N, out_dim] = model_orig.encode_text(tokens, normalize=normalize) (train/adversarial_training_clip.py:166-170,
+ * CLIP_eval/eval_utils.py:74-78): tokens [N, context] int32 on the device, N <= max_batch.  active_len: only the first active_len
+ * positions of every prompt are evaluated (the mask is causal: nothing behind a prompt's EOT reaches its EOT row); it must exceed
+ * every prompt's EOT position; 0 = the full context.  flags: optional device word, |= RVLM_FLAG_TOKEN_RANGE / RVLM_FLAG_EOT_ACTIVE
+ * (the call itself never faults on such input; the embeddings of that call are then meaningless). */
+int rvlm_text_encode(rvlm_text* h, const int32_t* tokens, int N, int active_len, int normalize, float* out_emb, uint32_t* flags,
+                     rvlm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement support: per-kernel-class HIP-event timing on the engine's stream.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
@@ -406,7 +453,8 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * rvlm_vit_backward_params_stages refuses out-of-order stages; 105: rvlm_apgd_controller_rho,
                            * rvlm_vit_set_apgd_rho, rvlm_comm_* / rvlm_allreduce_grads; 106: rvlm_pgd_run_mixed, fp32 mode on v_mfma_f32_32x32x2_f32;
                            * 107: rvlm_l2_random_start; 108: RVLM_PREC_F32X3 (split-bf16 linears over fp32 storage);
-                           * 109: rvlm_vit_backward_input_from, rvlm_vit_forward_for, rvlm_vit_set_flash_inference, rvlm_pgd_run_mixed_fwd (fp32-storage forward, bf16 backward) */
+                           * 109: rvlm_vit_backward_input_from, rvlm_vit_forward_for, rvlm_vit_set_flash_inference, rvlm_pgd_run_mixed_fwd (fp32-storage forward, bf16 backward);
+                           * still 109, additions only: rvlm_text_* (CLIP text tower, forward only, announced by RVLM_HAS_TEXT) */
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,16 @@ int rvlm_k_wgrad_bf16(const uint16_t* dY, long lddy, const uint16_t* X, long ldx
  * copy-free contraction-major GEMM - the A/B arm of tests and benches; 0 (default): the training step's path. */
 void rvlm_k_wgrad_set_transposed(int v);
 
+/* Text tower (csrc/attention_causal.hip, csrc/text_kernels.hip).  Causal flash attention forward on packed qkv [B*S, 3*64*H]
+ * (row i of a prompt attends to keys j <= i, scale 1/8), o [B*S, 64*H], S <= 96; only rows < active_len of every prompt are read and
+ * written (0 = S).  bf16 buffers as raw bits. */
+int rvlm_k_attn_causal_fwd_bf16(const uint16_t* qkv, uint16_t* o, int B, int H, int S, int active_len, rvlm_stream_t stream);
+int rvlm_k_attn_causal_fwd_f32(const float* qkv, float* o, int B, int H, int S, int active_len, rvlm_stream_t stream);
+/* x[n*active_len + t, :] = token_embedding[tokens[n, t], :] + positional_embedding[t, :] (tokens [N, context] int32), eot[n] = first
+ * position of prompt n's largest id; flags (optional) |= RVLM_FLAG_TOKEN_RANGE / RVLM_FLAG_EOT_ACTIVE.  active_len 0 = context. */
+int rvlm_k_text_embed(const int32_t* tokens, const float* token_embedding, const float* positional_embedding, float* x, int32_t* eot,
+                      uint32_t* flags, int N, int context, int active_len, int vocab, int W, rvlm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,10 +12,14 @@ arithmetic op runs in the in-tree HIP library ``librvlm.so`` (include/rvlm.h):
       ::ComputeLossWrapper/compute_loss/l2/ce           robustvlm_amd.{ComputeLossWrapper,...}
     CLIP_eval/clip_robustbench.py::ClassificationModel  robustvlm_amd.ClassificationModel
     open_clip VisionTransformer (third party)           robustvlm_amd.VitEngine
+    open_clip CLIP.encode_text (third party)            robustvlm_amd.{TextEngine,ClipTextModel}
+    CLIP_eval/eval_utils.py::get_text_embeddings        robustvlm_amd.get_text_embeddings
 """
-from .config import VitConfig, CONFIGS, CLIP_MEAN, CLIP_STD, random_state_dict, state_dict_shapes
+from .config import (VitConfig, CONFIGS, CLIP_MEAN, CLIP_STD, random_state_dict, state_dict_shapes, TextConfig, TEXT_CONFIGS,
+                     text_state_dict_shapes, random_text_state_dict)
 from .engine import VitEngine
-from .clip_model import (ClipVisionModel, ComputeLossWrapper, ClassificationModel, compute_loss, l2, ce,
+from .text_engine import TextEngine
+from .clip_model import (ClipVisionModel, ClipTextModel, ComputeLossWrapper, ClassificationModel, compute_loss, l2, ce,
                          compute_acc)
 from .attack_utils import project_perturbation, normalize_grad
 from .pgd_train import pgd
@@ -23,11 +27,13 @@ from .apgd_train import apgd_train
 from .autopgd import APGDAttack, APGDAttack_targeted
 from .autoattack import AutoAttack, EvaluationState
 from .square import SquareAttack
-from .eval_utils import compute_accuracy_no_dataloader, zeroshot_head
+from .eval_utils import compute_accuracy_no_dataloader, zeroshot_head, get_text_embeddings, get_text_embeddings_ensemble
 from .preprocess import ResizeCenterCropToTensor
-from .checkpoint import load_visual_state_dict, CheckpointWriter, resume_paths
+from .checkpoint import load_visual_state_dict, load_text_state_dict, CheckpointWriter, resume_paths
 
 __all__ = ["VitConfig", "CONFIGS", "CLIP_MEAN", "CLIP_STD", "random_state_dict", "state_dict_shapes",
            "VitEngine", "ClipVisionModel", "ComputeLossWrapper", "ClassificationModel", "compute_loss",
            "l2", "ce", "compute_acc", "project_perturbation", "normalize_grad", "pgd", "apgd_train",
-           "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths"]
+           "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths",
+           "TextConfig", "TEXT_CONFIGS", "text_state_dict_shapes", "random_text_state_dict", "TextEngine", "ClipTextModel",
+           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict"]

@@ -19,6 +19,7 @@ ACT_QUICK_GELU, ACT_GELU = 0, 1
 LOSS_L2, LOSS_CE, LOSS_DLR, LOSS_DLR_TARGETED = 0, 1, 2, 3
 RED_MEAN, RED_NONE = 0, 1
 FLAG_INPUT_RANGE, FLAG_NAN_GRAD, FLAG_NAN_DELTA, FLAG_ADV_RANGE = 1, 2, 4, 8
+FLAG_TOKEN_RANGE, FLAG_EOT_ACTIVE = 16, 32
 
 c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 c_stream = C.c_void_p
@@ -57,6 +58,22 @@ TOP_KEYS = {"class_embedding": "class_embedding", "positional_embedding": "posit
 
 class VitWeightsC(C.Structure):
     _fields_ = [(f, C.c_void_p) for f in TOP_FIELDS] + [("blocks_host", C.POINTER(BlockWeightsC))]
+
+
+class TextConfigC(C.Structure):
+    _fields_ = [("vocab", C.c_int32), ("context", C.c_int32), ("width", C.c_int32), ("layers", C.c_int32),
+                ("heads", C.c_int32), ("out_dim", C.c_int32), ("act", C.c_int32), ("precision", C.c_int32),
+                ("max_batch", C.c_int32)]
+
+
+TEXT_TOP_FIELDS = ["token_embedding", "positional_embedding", "ln_final_weight", "ln_final_bias", "text_projection"]
+TEXT_TOP_KEYS = {"token_embedding": "token_embedding.weight", "positional_embedding": "positional_embedding",
+                 "ln_final_weight": "ln_final.weight", "ln_final_bias": "ln_final.bias",
+                 "text_projection": "text_projection"}
+
+
+class TextWeightsC(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in TEXT_TOP_FIELDS] + [("blocks_host", C.POINTER(BlockWeightsC))]
 
 
 class LossSpecC(C.Structure):
@@ -209,6 +226,17 @@ _SIGS.update({
     "rvlm_allreduce_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, c_stream]),
 })
 COMM_ID_BYTES, DTYPE_F32, DTYPE_BF16 = 128, 0, 1
+_SIGS.update({
+    # text tower (csrc/text_engine.hip): forward-only handle + the kernel-level hooks of its own kernels
+    "rvlm_text_create": (C.c_int, [C.POINTER(TextConfigC), C.POINTER(TextWeightsC), c_stream, C.POINTER(C.c_void_p)]),
+    "rvlm_text_destroy": (C.c_int, [C.c_void_p]),
+    "rvlm_text_workspace_bytes": (C.c_size_t, [C.c_void_p]),
+    "rvlm_text_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_stream]),
+    "rvlm_k_attn_causal_fwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_attn_causal_fwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_text_embed": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

@@ -22,7 +22,7 @@ import os
 
 import torch
 
-from .config import VitConfig, state_dict_shapes
+from .config import VitConfig, TextConfig, state_dict_shapes, text_state_dict_shapes
 
 
 def load_visual_state_dict(checkpoint, cfg: VitConfig | None = None, map_location="cpu") -> dict:
@@ -40,6 +40,30 @@ def load_visual_state_dict(checkpoint, cfg: VitConfig | None = None, map_locatio
             if tuple(checkpoint[k].shape) != tuple(shp):
                 raise ValueError(f"{k}: checkpoint shape {tuple(checkpoint[k].shape)} != {tuple(shp)}")
     return checkpoint
+
+
+def load_text_state_dict(checkpoint, cfg: TextConfig | None = None, map_location="cpu") -> dict:
+    """The text tower's weights out of a full open_clip ``CLIP.state_dict()`` (a path or an already-loaded object): every
+    key outside ``visual.`` except ``logit_scale`` and the ``attn_mask`` buffer - what ``model_orig.encode_text`` reads
+    (train/adversarial_training_clip.py:95-97,166-170).  Validated against ``cfg`` when given."""
+    if isinstance(checkpoint, (str, os.PathLike)):
+        checkpoint = torch.load(checkpoint, map_location=map_location)
+    if "state_dict" in checkpoint.keys():
+        checkpoint = checkpoint["state_dict"]
+    sd = {k: v for k, v in checkpoint.items()
+          if not k.startswith("visual.") and k not in ("logit_scale", "logit_bias", "attn_mask")}
+    if cfg is not None:
+        shapes = text_state_dict_shapes(cfg)
+        missing = [k for k in shapes if k not in sd]
+        if missing:
+            raise KeyError(f"checkpoint is missing {len(missing)} text keys, e.g. {missing[:3]}")
+        unexpected = [k for k in sd if k not in shapes]
+        if unexpected:
+            raise KeyError(f"checkpoint has {len(unexpected)} unexpected non-visual keys, e.g. {unexpected[:3]}")
+        for k, shp in shapes.items():
+            if tuple(sd[k].shape) != tuple(shp):
+                raise ValueError(f"{k}: checkpoint shape {tuple(sd[k].shape)} != {tuple(shp)}")
+    return sd
 
 
 def resume_paths(optimizer_state: str, start_step: int):

@@ -6,6 +6,7 @@ Mirrors (same names, argument meaning and error behaviour):
   compute_loss, l2, ce train/adversarial_training_clip.py:495-528
   compute_acc          train/adversarial_training_clip.py:488-492
   ClassificationModel  CLIP_eval/clip_robustbench.py:50-69
+  ClipTextModel        open_clip CLIP.encode_text as called at train/adversarial_training_clip.py:166-170
 
 The arithmetic runs in librvlm.so: ``ClipVisionModel.forward`` is a torch.autograd.Function over
 rvlm_vit_forward / rvlm_vit_backward_input (so even the reference's unmodified ``pgd`` can
@@ -17,6 +18,7 @@ import torch
 
 from . import _lib as L
 from .engine import VitEngine, _require_cuda, _f32c
+from .text_engine import TextEngine
 
 
 class _EncodeFn(torch.autograd.Function):
@@ -60,6 +62,24 @@ class ClipVisionModel(torch.nn.Module):
     def forward(self, vision, output_normalize):
         _require_cuda(vision, "vision")
         return _EncodeFn.apply(vision, self.model, bool(output_normalize))
+
+
+class ClipTextModel(torch.nn.Module):
+    """``encode_text(text, normalize=False)`` with open_clip's signature over a :class:`TextEngine` - the text half of
+    the frozen ``model_orig`` (train/adversarial_training_clip.py:166-170, CLIP_eval/eval_utils.py:74-78).  Forward only:
+    the result carries no graph.  ``text`` is what ``open_clip.tokenize`` returns, on the CPU or the device."""
+
+    def __init__(self, model: TextEngine):
+        super().__init__()
+        if not isinstance(model, TextEngine):
+            raise TypeError("ClipTextModel expects a robustvlm_amd.TextEngine as `model`")
+        self.model = model
+
+    def encode_text(self, text, normalize: bool = False):
+        return self.model.encode(text, normalize=bool(normalize))
+
+    def forward(self, text, normalize: bool = False):
+        return self.encode_text(text, normalize)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -2,7 +2,10 @@
 
 * :func:`compute_accuracy_no_dataloader` - CLIP_eval/eval_utils.py:88-112
 * :func:`zeroshot_head`                  - the prompt-ensembling arithmetic of CLIP_eval/clip_robustbench.py:211-224
-  (the text tower itself is out of scope: pass the per-template text embeddings)
+* :func:`get_text_embeddings`            - CLIP_eval/eval_utils.py:63-85 (one template per class) on the native text tower
+* :func:`get_text_embeddings_ensemble`   - CLIP_eval/clip_robustbench.py:211-224 (template ensemble) on the native text tower
+
+Tokenisation stays with the caller: both take the integer ids ``open_clip.tokenize`` returns.
 """
 from __future__ import annotations
 
@@ -45,3 +48,26 @@ def zeroshot_head(template_embeddings) -> torch.Tensor:
     T = torch.stack(cols, dim=1)
     assert torch.allclose(F.normalize(T, dim=0), T, atol=1e-6)
     return T
+
+
+@torch.no_grad()
+def get_text_embeddings(text_model, tokens) -> torch.Tensor:
+    """``embedding_text_labels_norm`` [D, C] from the token ids [C, context] of one prompt per class:
+    ``encode_text(tokens, normalize=True).T`` (CLIP_eval/eval_utils.py:74-80, train/adversarial_training_clip.py:163-172; the
+    reference's chunks of 500 prompts are the engine's ``max_batch``).  ``text_model``: a ClipTextModel (or TextEngine)."""
+    enc = text_model.encode_text if hasattr(text_model, "encode_text") else text_model.encode
+    T = enc(tokens, normalize=True).T.contiguous()
+    assert torch.allclose(F.normalize(T, dim=0), T, atol=1e-6)
+    return T
+
+
+@torch.no_grad()
+def get_text_embeddings_ensemble(text_model, tokens) -> torch.Tensor:
+    """The template-ensemble head [D, C] from token ids [C, n_templates, context] (CLIP_eval/clip_robustbench.py:211-224):
+    un-normalised ``encode_text`` of every prompt, then :func:`zeroshot_head`."""
+    if tokens.dim() != 3:
+        raise ValueError(f"tokens must be [C, n_templates, context], got {tuple(tokens.shape)}")
+    enc = text_model.encode_text if hasattr(text_model, "encode_text") else text_model.encode
+    C_, n_t, ctx = tokens.shape
+    emb = enc(tokens.reshape(C_ * n_t, ctx), normalize=False)
+    return zeroshot_head(emb.reshape(C_, n_t, -1))
