@@ -29,6 +29,8 @@ extern "C" {
 /* Additions made without a version step are announced by a feature macro (a binding can also probe the symbol):
  * RVLM_HAS_TEXT: the rvlm_text_* entry points and RVLM_FLAG_TOKEN_RANGE / RVLM_FLAG_EOT_ACTIVE */
 #define RVLM_HAS_TEXT 1
+/* RVLM_HAS_FAB: the rvlm_fab_* entry points (FAB / FAB-T, L-inf), RVLM_LOSS_LOGIT_DIFF and RVLM_FLAG_FAB_NONFINITE */
+#define RVLM_HAS_FAB 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -47,7 +49,8 @@ typedef enum {
 enum { RVLM_PREC_F32 = 0, RVLM_PREC_BF16 = 1, RVLM_PREC_F32X3 = 2 };
 enum { RVLM_ACT_QUICK_GELU = 0, RVLM_ACT_GELU = 1 };  /* open_clip QuickGELU / exact erf GELU */
 enum { RVLM_LOSS_L2 = 0, RVLM_LOSS_CE = 1,             /* FARE l2 / TeCoA ce (…clip.py:495-528) */
-       RVLM_LOSS_DLR = 2, RVLM_LOSS_DLR_TARGETED = 3 }; /* AutoAttack DLR losses (autopgd_base.py:195-201, 613-618) */
+       RVLM_LOSS_DLR = 2, RVLM_LOSS_DLR_TARGETED = 3,   /* AutoAttack DLR losses (autopgd_base.py:195-201, 613-618) */
+       RVLM_LOSS_LOGIT_DIFF = 4 };                      /* FAB-T's logit difference (fab_pt.py:100-114), RVLM_HAS_FAB */
 enum { RVLM_RED_MEAN = 0, RVLM_RED_NONE = 1 };        /* reduction='mean' | 'none' (grad of sum) */
 
 /* bits of the device-side flag word written by the attack kernels (replaces the reference's
@@ -59,7 +62,9 @@ enum {
     RVLM_FLAG_ADV_RANGE = 8,   /* x+delta left [0,1] (+-1e-6)                pgd_train.py:61-63 */
     /* rvlm_text_encode (RVLM_HAS_TEXT); where the reference would fault inside nn.Embedding or pool the wrong row */
     RVLM_FLAG_TOKEN_RANGE = 16, /* a token id outside [0, vocab)                                  */
-    RVLM_FLAG_EOT_ACTIVE = 32   /* a prompt's EOT position (argmax of its ids) is >= active_len   */
+    RVLM_FLAG_EOT_ACTIVE = 32,  /* a prompt's EOT position (argmax of its ids) is >= active_len   */
+    /* rvlm_fab_projection_linf / rvlm_fab_linf_step (RVLM_HAS_FAB) */
+    RVLM_FLAG_FAB_NONFINITE = 64 /* NaN / Inf in a row's w, t or b: that row gets lambda = 0 (no move) */
 };
 
 /* ---------------------------------------------------------------------------------------------
@@ -178,8 +183,11 @@ int rvlm_adamw_step(float* params, const float* grads, float* exp_avg, float* ex
  *        -(z_y - max_{c != y} z_c) / (z_(1) - z_(3) + 1e-12)            resp.
  *        -(z_y - z_t) / (z_(1) - (z_(3) + z_(4)) / 2 + 1e-12),  t = y_target[b],  z_(k) = k-th largest logit
  * reduction MEAN: *loss_scalar = mean_b, d_emb carries the 1/B; NONE: d_emb = grad of the sum.
+ *   LOGIT_DIFF (FAB-T, fab_pt.py:100-114; RVLM_HAS_FAB): same logits; per_sample = -(z_y - z_t), t = y_target[b];
+ *        d_emb = logit_scale * (T[:, t] - T[:, y]): with reduction NONE one call gives FAB's df (per_sample) and, through
+ *        rvlm_vit_fwd_inputgrad, dg (grad_x) without an autograd graph.
  * pred_eq (optional, u8[B]) = argmax_c(logits) == targets (head losses only).  scratch: the head losses need
- * B*C + D*C floats (may be NULL for L2).  y_target: DLR_TARGETED only (else NULL).
+ * B*C + D*C floats (may be NULL for L2).  y_target: DLR_TARGETED and LOGIT_DIFF (else NULL).
  * ------------------------------------------------------------------------------------------- */
 int rvlm_loss_grad(int loss_kind, int reduction, const float* emb, const float* ref,
                    const int64_t* targets, const int64_t* y_target, int B, int D, int C, float logit_scale,
@@ -278,6 +286,36 @@ int rvlm_square_accept(float* x_best, const float* x_new, const int64_t* idx, co
                        size_t n_per_image, rvlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * FAB / FAB-T, L-inf (RVLM_HAS_FAB): the device arithmetic of one iteration of FABAttack.attack_single_run
+ * (autoattack/fab_base.py:160-254).  The loop itself is sequenced by the host (robustvlm_amd/fab.py) without a
+ * synchronisation; scratch and state are the caller's tensors.  One workgroup per row / image, deterministic sums.
+ * ------------------------------------------------------------------------------------------- */
+/* projection_linf (autoattack/fab_projections.py:7-58) without the sort: for each of R rows, d [R, D] with the smallest
+ * max|d_i| such that w.(t + d) = b and 0 <= t + d <= 1 - d_i = dir_i * min(lambda, room_i), dir_i = sign(b - w.t) sign(w_i),
+ * room_i = distance of t_i to the box face in that direction (0 where w_i = 0), lambda the smallest fp32 with
+ * sum_i |w_i| min(lambda, room_i) >= |b - w.t|; every coordinate to its face when the hyperplane misses the box.
+ * lambda (optional, [R]) = max_i |d_i|.  flags (optional) |= RVLM_FLAG_FAB_NONFINITE for a row with NaN / Inf, whose d is 0.
+ * The search is a fixed number of passes whatever the data. */
+int rvlm_fab_projection_linf(const float* t, const float* w, const float* b, int R, size_t D, float* d, float* lambda,
+                             int32_t* flags, rvlm_stream_t stream);
+/* fab_base.py:166-226 for B images of n_per_sample pixels given the chosen class' df [B] and dg [B, n]: b = -df + dg.x1, the
+ * projections d1 of x1 and d0 of x0 (the clean image) onto dg.z = b, alpha = min(max(a1 / (a1 + a0), 0), alpha_max) with
+ * a = max(max|d|, 1e-8), and IN PLACE x1 = clamp((x1 + eta d1) (1 - alpha) + (x0 + eta d0) alpha, 0, 1); d1 / d0 are never
+ * stored.  lambda (optional, [B, 2]) = max|d1|, max|d0|. */
+int rvlm_fab_linf_step(float* x1, const float* x0, const float* dg, const float* df, int B, size_t n_per_sample,
+                       float alpha_max, float eta, float* lambda, int32_t* flags, rvlm_stream_t stream);
+/* fab_base.py:228-252 after the prediction forward: for the images with pred_eq[b] == 0 (x1 is misclassified),
+ * t = max|x1 - x0|; t < res2[b] -> adv[b] = x1[b], res2[b] = t; then the backward step x1 = x0 + (x1 - x0) * beta. */
+int rvlm_fab_track_best(float* x1, const float* x0, float* adv, float* res2, const uint8_t* pred_eq, float beta, int B,
+                        size_t n_per_sample, rvlm_stream_t stream);
+/* Untargeted FAB, class k of the Jacobian streamed class by class instead of the [K, B, D] tensor of fab_pt.py:76-98:
+ * w = g_k - g_y, dist = |df_k| / (1e-12 + |w|_1) (fab_base.py:166-170); where y[b] != k and dist < best_dist[b] (strictly:
+ * the first minimum wins like min(dim=1)[1], :181) -> best_dist[b] = dist, best_df[b] = df_k[b], best_w[b] = w.  The caller
+ * starts best_dist at +inf and calls k = 0 .. K-1 in order. */
+int rvlm_fab_jacobian_argmin(const float* g_k, const float* g_y, const float* df_k, const int64_t* y, int k, int B,
+                             size_t n_per_sample, float* best_dist, float* best_df, float* best_w, rvlm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Whole loops, device resident (no host sync inside): replace
  *   pgd()        train/pgd_train.py:5-68          -> rvlm_pgd_run
  *   apgd_train() train/apgd_train.py:125-373      -> rvlm_apgd_run (train_variant = 1)
@@ -292,7 +330,7 @@ typedef struct {
     float logit_scale;        /* 100. */
     const float* ref;         /* L2: embedding_orig [B,D];  CE: T [D,C] */
     const int64_t* targets;   /* [B] (CE, and the argmax test of apgd); may be NULL for pgd+L2 */
-    const int64_t* y_target;  /* [B] target classes, RVLM_LOSS_DLR_TARGETED only (else NULL) */
+    const int64_t* y_target;  /* [B] target classes, RVLM_LOSS_DLR_TARGETED / RVLM_LOSS_LOGIT_DIFF (else NULL) */
 } rvlm_loss_spec;
 
 /* x_adv_out = pgd(...) ; delta0 may be NULL (zeros).  flags: see RVLM_FLAG_*.
@@ -454,7 +492,8 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * rvlm_vit_set_apgd_rho, rvlm_comm_* / rvlm_allreduce_grads; 106: rvlm_pgd_run_mixed, fp32 mode on v_mfma_f32_32x32x2_f32;
                            * 107: rvlm_l2_random_start; 108: RVLM_PREC_F32X3 (split-bf16 linears over fp32 storage);
                            * 109: rvlm_vit_backward_input_from, rvlm_vit_forward_for, rvlm_vit_set_flash_inference, rvlm_pgd_run_mixed_fwd (fp32-storage forward, bf16 backward);
-                           * still 109, additions only: rvlm_text_* (CLIP text tower, forward only, announced by RVLM_HAS_TEXT) */
+                           * still 109, additions only: rvlm_text_* (CLIP text tower, forward only, announced by RVLM_HAS_TEXT);
+                           * rvlm_fab_* (FAB / FAB-T L-inf), RVLM_LOSS_LOGIT_DIFF, RVLM_FLAG_FAB_NONFINITE (announced by RVLM_HAS_FAB) */
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,7 @@ arithmetic op runs in the in-tree HIP library ``librvlm.so`` (include/rvlm.h):
     train/pgd_train.py::pgd                             robustvlm_amd.pgd
     train/apgd_train.py::apgd_train                     robustvlm_amd.apgd_train
     autoattack/autopgd_base.py::APGDAttack              robustvlm_amd.APGDAttack
+    autoattack/fab_pt.py::FABAttack_PT                  robustvlm_amd.FABAttack
     vlm_eval/attacks/utils.py                           robustvlm_amd.attack_utils
     train/adversarial_training_clip.py::ClipVisionModel robustvlm_amd.ClipVisionModel
       ::ComputeLossWrapper/compute_loss/l2/ce           robustvlm_amd.{ComputeLossWrapper,...}
@@ -27,6 +28,7 @@ from .apgd_train import apgd_train
 from .autopgd import APGDAttack, APGDAttack_targeted
 from .autoattack import AutoAttack, EvaluationState
 from .square import SquareAttack
+from .fab import FABAttack
 from .eval_utils import compute_accuracy_no_dataloader, zeroshot_head, get_text_embeddings, get_text_embeddings_ensemble
 from .preprocess import ResizeCenterCropToTensor
 from .checkpoint import load_visual_state_dict, load_text_state_dict, CheckpointWriter, resume_paths
@@ -34,6 +36,6 @@ from .checkpoint import load_visual_state_dict, load_text_state_dict, Checkpoint
 __all__ = ["VitConfig", "CONFIGS", "CLIP_MEAN", "CLIP_STD", "random_state_dict", "state_dict_shapes",
            "VitEngine", "ClipVisionModel", "ComputeLossWrapper", "ClassificationModel", "compute_loss",
            "l2", "ce", "compute_acc", "project_perturbation", "normalize_grad", "pgd", "apgd_train",
-           "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths",
+           "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "FABAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths",
            "TextConfig", "TEXT_CONFIGS", "text_state_dict_shapes", "random_text_state_dict", "TextEngine", "ClipTextModel",
            "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict"]

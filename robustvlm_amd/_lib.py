@@ -16,10 +16,11 @@ LIB_PATH = os.path.abspath(os.environ["RVLM_LIB_PATH"]) if os.environ.get("RVLM_
 RVLM_OK, RVLM_ERR_ARG, RVLM_ERR_HIP, RVLM_ERR_STATE, RVLM_ERR_UNSUPPORTED = 0, 1, 2, 3, 4
 PREC_F32, PREC_BF16, PREC_F32X3 = 0, 1, 2
 ACT_QUICK_GELU, ACT_GELU = 0, 1
-LOSS_L2, LOSS_CE, LOSS_DLR, LOSS_DLR_TARGETED = 0, 1, 2, 3
+LOSS_L2, LOSS_CE, LOSS_DLR, LOSS_DLR_TARGETED, LOSS_LOGIT_DIFF = 0, 1, 2, 3, 4
 RED_MEAN, RED_NONE = 0, 1
 FLAG_INPUT_RANGE, FLAG_NAN_GRAD, FLAG_NAN_DELTA, FLAG_ADV_RANGE = 1, 2, 4, 8
 FLAG_TOKEN_RANGE, FLAG_EOT_ACTIVE = 16, 32
+FLAG_FAB_NONFINITE = 64
 
 c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 c_stream = C.c_void_p
@@ -236,6 +237,15 @@ _SIGS.update({
     "rvlm_k_attn_causal_fwd_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "rvlm_k_text_embed": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                     C.c_int, C.c_int, c_stream]),
+})
+_SIGS.update({
+    # FAB / FAB-T, L-inf (csrc/fab_kernels.hip)
+    "rvlm_fab_projection_linf": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int, C.c_size_t, c_f32p, c_f32p, C.c_void_p, c_stream]),
+    "rvlm_fab_linf_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_size_t, C.c_float, C.c_float, c_f32p,
+                                     C.c_void_p, c_stream]),
+    "rvlm_fab_track_best": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_float, C.c_int, C.c_size_t, c_stream]),
+    "rvlm_fab_jacobian_argmin": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, c_f32p, c_f32p,
+                                           c_f32p, c_stream]),
 })
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

@@ -6,10 +6,12 @@ iterations_apgd=..., use_rs=...)`` then ``run_standard_evaluation(x, y, bs=...)`
 native :class:`~robustvlm_amd.autopgd.APGDAttack` / :class:`~robustvlm_amd.autopgd.APGDAttack_targeted` (whole loops on
 the device when ``model`` is a :class:`~robustvlm_amd.clip_model.ClassificationModel` over the engine).
 
-Built: ``apgd-ce``, ``apgd-dlr``, ``apgd-t`` and ``square`` (the black-box route of clip_robustbench.py:150-151, L-inf;
-:class:`~robustvlm_amd.square.SquareAttack`).  NOT built (the reference's configs for this path never select them):
-``fab``, ``fab-t`` -> NotImplementedError when they would run; their hyper-parameter holder exists so that
-``set_version`` and user code that tweaks ``adversary.fab.n_restarts`` keep working.
+Built: ``apgd-ce``, ``apgd-dlr``, ``apgd-t``, ``square`` (the black-box route of clip_robustbench.py:150-151, L-inf;
+:class:`~robustvlm_amd.square.SquareAttack`) and ``fab`` / ``fab-t`` (L-inf; :class:`~robustvlm_amd.fab.FABAttack`), so
+``version='standard'`` and ``'plus'`` run end to end for ``norm='Linf'``.  Square and FAB have no L2 / L1 form and FAB has
+no CPU path: where they cannot run (another norm, an attack device or inputs that are not a GPU) the pre-flight check of
+``run_standard_evaluation`` raises NotImplementedError before any attack time is spent; their hyper-parameter holder
+exists in every case so that ``set_version`` and user code that tweaks ``adversary.fab.n_restarts`` keep working.
 """
 from __future__ import annotations
 
@@ -26,10 +28,11 @@ import numpy as np
 import torch
 
 from .autopgd import APGDAttack, APGDAttack_targeted
+from .fab import FABAttack
 from .square import SquareAttack
 
-_BUILT = ("apgd-ce", "apgd-dlr", "apgd-t", "square")
-_KNOWN = _BUILT + ("fab", "fab-t")
+_BUILT = ("apgd-ce", "apgd-dlr", "apgd-t", "square", "fab", "fab-t")
+_KNOWN = _BUILT
 
 
 class EvaluationState:
@@ -133,8 +136,12 @@ class AutoAttack():
                       device=device, logger=self.logger, alpha=alpha, use_rs=use_rs)
         self.apgd = APGDAttack(model, n_restarts=5, **common)                       # autoattack.py:34-36
         self.apgd_targeted = APGDAttack_targeted(model, n_restarts=1, **common)     # :47-49
-        # hyper-parameter holders of the attacks that are not built (see module docstring)
-        self.fab = SimpleNamespace(n_restarts=5, n_iter=100, n_target_classes=9, targeted=False, seed=seed)
+        # L-inf only attacks; otherwise hyper-parameter holders (see module docstring)
+        if norm == 'Linf':                                                          # autoattack.py:38-40
+            self.fab = FABAttack(model, n_restarts=5, n_iter=100, eps=eps, seed=seed, norm=norm, verbose=False,
+                                 device=device)
+        else:
+            self.fab = SimpleNamespace(n_restarts=5, n_iter=100, n_target_classes=9, targeted=False, seed=seed)
         if norm == 'Linf':                                                          # autoattack.py:42-44
             self.square = SquareAttack(model, p_init=.8, n_queries=5000, eps=eps, norm=norm, n_restarts=1, seed=seed,
                                        verbose=False, device=device, resc_schedule=False)
@@ -214,9 +221,27 @@ class AutoAttack():
         if attack == 'square' and isinstance(self.square, SquareAttack):
             self.square.seed = self.get_seed()
             return self.square.perturb(x, y)
+        if attack in ('fab', 'fab-t') and isinstance(self.fab, FABAttack):       # autoattack.py:196-200, 212-217
+            self.fab.targeted = attack == 'fab-t'
+            if attack == 'fab-t':
+                self.fab.n_restarts = 1
+            self.fab.seed = self.get_seed()
+            return self.fab.perturb(x, y)
         if attack in _KNOWN:
-            raise NotImplementedError(f"attack '{attack}' is not part of the native path (built: {', '.join(_BUILT)})")
+            raise NotImplementedError(f"attack '{attack}' is not available here: {self._unavailable(attack)}")
         raise ValueError('Attack not supported')
+
+    def _unavailable(self, attack):
+        """Why a known attack cannot run in this configuration ('' if it can): Square and FAB are L-inf only, FAB has no
+        CPU path (its projection and bookkeeping are HIP kernels)."""
+        if attack == 'square' and not isinstance(self.square, SquareAttack):
+            return f"square is built for norm='Linf' only (norm={self.norm!r})"
+        if attack in ('fab', 'fab-t'):
+            if not isinstance(self.fab, FABAttack):
+                return f"{attack} is built for norm='Linf' only (norm={self.norm!r})"
+            if torch.device(self.device).type != 'cuda':
+                return f"{attack} runs on the GPU only (attack device {self.device!r}); there is no CPU fallback"
+        return ''
 
     # ------------------------------------------------------------------------------------------ evaluation
     def run_standard_evaluation(self, x_orig, y_orig, bs=250, return_labels=False, state_path=None):
@@ -234,11 +259,9 @@ class AutoAttack():
             if state_path is not None:
                 self._say("Created state in {}".format(state_path))
         todo = [a for a in self.attacks_to_run if a not in state.run_attacks]
-        missing = [a for a in todo if a in _KNOWN and (a not in _BUILT or (a == 'square' and not isinstance(
-            self.square, SquareAttack)))]
-        if missing:       # fail before hours of attack time are spent, not when the unbuilt attack's turn comes
-            raise NotImplementedError(f"attack(s) {missing} are not part of the native path (built: {', '.join(_BUILT)}; "
-                                      f"square is L-inf only)")
+        missing = {a: self._unavailable(a) for a in todo if a in _KNOWN and self._unavailable(a)}
+        if missing:       # fail before hours of attack time are spent, not when the attack's turn comes
+            raise NotImplementedError("attack(s) that cannot run here: " + "; ".join(missing.values()))
         self._say('using {} version including {}.'.format(self.version, ', '.join(todo)))
         if state.run_attacks:
             self._say('{} was/were already run.'.format(', '.join(state.run_attacks)))

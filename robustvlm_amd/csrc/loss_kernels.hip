@@ -138,6 +138,37 @@ dlr_loss_kernel(float* __restrict__ logits, const int64_t* __restrict__ targets,
     }
 }
 
+// FAB-T's logit difference on a logits row (autoattack/fab_pt.py:100-114), one wave per row: per_sample = -(z_y - z_t),
+// d loss / d logits = -1 at y, +1 at t (0 where y == t) written in place; pred_eq = (arg-max == y), ties -> first index
+__global__ void __launch_bounds__(256)
+logit_diff_kernel(float* __restrict__ logits, const int64_t* __restrict__ targets, const int64_t* __restrict__ y_target,
+                  int B, int C, float gscale, float* __restrict__ per_sample, uint8_t* __restrict__ pred_eq, int write_grad) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    float* l = logits + (long)row * C;
+    const int y = (int)targets[row], yt = (int)y_target[row];
+    float m = -INFINITY;
+    int mi = 0x7fffffff;
+    for (int c = lane; c < C; c += 64) {
+        const float v = l[c];
+        if (v > m) { m = v; mi = c; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64);
+        const int oi = __shfl_xor(mi, o, 64);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    const float zy = l[y], zt = l[yt];
+    if (lane == 0) {
+        if (per_sample) per_sample[row] = -(zy - zt);
+        if (pred_eq) pred_eq[row] = (mi == y) ? 1 : 0;
+    }
+    if (write_grad) {
+        for (int c = lane; c < C; c += 64) l[c] = ((c == yt ? 1.0f : 0.0f) - (c == y ? 1.0f : 0.0f)) * gscale;
+    }
+}
+
 // deterministic single-block reduction of the per-sample losses -> scalar
 __global__ void __launch_bounds__(256)
 reduce_loss_kernel(const float* __restrict__ per_sample, int B, float scale, float* __restrict__ out) {
@@ -205,11 +236,13 @@ extern "C" int rvlm_loss_grad(int loss_kind, int reduction, const float* emb, co
         hipLaunchKernelGGL(l2_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, emb, ref, B, D, gscale,
                            loss_per_sample, d_emb);
         RVLM_CHECK_LAUNCH();
-    } else if (loss_kind == RVLM_LOSS_CE || loss_kind == RVLM_LOSS_DLR || loss_kind == RVLM_LOSS_DLR_TARGETED) {
+    } else if (loss_kind == RVLM_LOSS_CE || loss_kind == RVLM_LOSS_DLR || loss_kind == RVLM_LOSS_DLR_TARGETED ||
+               loss_kind == RVLM_LOSS_LOGIT_DIFF) {
         RVLM_REQUIRE(targets && scratch && C > 0, "rvlm_loss_grad: head losses need targets, scratch, C");
         RVLM_REQUIRE(loss_kind != RVLM_LOSS_DLR_TARGETED || y_target, "rvlm_loss_grad: dlr-targeted needs y_target");
+        RVLM_REQUIRE(loss_kind != RVLM_LOSS_LOGIT_DIFF || y_target, "rvlm_loss_grad: logit-diff needs y_target");
         // checks.check_n_classes: the DLR loss needs 3 logits, its targeted form 4
-        RVLM_REQUIRE(loss_kind == RVLM_LOSS_CE || C >= (loss_kind == RVLM_LOSS_DLR ? 3 : 4),
+        RVLM_REQUIRE(loss_kind == RVLM_LOSS_CE || loss_kind == RVLM_LOSS_LOGIT_DIFF || C >= (loss_kind == RVLM_LOSS_DLR ? 3 : 4),
                      "rvlm_loss_grad: too few classes for the DLR loss");
         RVLM_REQUIRE(loss_per_sample || !loss_scalar, "rvlm_loss_grad: loss_scalar needs loss_per_sample");
         float* logits = scratch;                 // [B, C]
@@ -226,6 +259,9 @@ extern "C" int rvlm_loss_grad(int loss_kind, int reduction, const float* emb, co
         if (loss_kind == RVLM_LOSS_CE)
             hipLaunchKernelGGL(ce_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, logits, targets, B, C,
                                gscale, loss_per_sample, pred_eq, d_emb ? 1 : 0);
+        else if (loss_kind == RVLM_LOSS_LOGIT_DIFF)
+            hipLaunchKernelGGL(logit_diff_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, logits, targets, y_target, B, C, gscale,
+                               loss_per_sample, pred_eq, d_emb ? 1 : 0);
         else
             hipLaunchKernelGGL(dlr_loss_kernel, dim3(cdiv(B, 4)), dim3(256), 0, s, logits, targets,
                                loss_kind == RVLM_LOSS_DLR_TARGETED ? y_target : (const int64_t*)nullptr, B, C, gscale,

@@ -224,16 +224,17 @@ class VitEngine:
         self.generation += 1
         return emb, g
 
-    def fwd_inputgrad(self, x, delta, loss_kind, reduction, ref, targets, output_normalize, logit_scale=100.0):
+    def fwd_inputgrad(self, x, delta, loss_kind, reduction, ref, targets, output_normalize, logit_scale=100.0, y_target=None):
         """One iteration's model work in one native call (rvlm_vit_fwd_inputgrad): returns
-        (emb, loss_per_sample, loss_scalar, grad_x)."""
+        (emb, loss_per_sample, loss_scalar, grad_x).  y_target: the target classes of 'dlr-targeted' / 'logit-diff'."""
         self._check_images(x)
         x = _f32c(x)
         d = _f32c(delta) if delta is not None else None
         ref = _f32c(ref)
         tg = targets.detach().to(torch.int64).contiguous() if isinstance(targets, torch.Tensor) else None
         B = x.shape[0]
-        ls = self._loss_spec(loss_kind, reduction, output_normalize, ref, tg, logit_scale, B=B)
+        yt = y_target.detach().to(torch.int64).contiguous() if isinstance(y_target, torch.Tensor) else None
+        ls = self._loss_spec(loss_kind, reduction, output_normalize, ref, tg, logit_scale, y_target=yt, B=B)
         emb = torch.empty(B, self.cfg.out_dim, device=x.device, dtype=torch.float32)
         per = torch.empty(B, device=x.device, dtype=torch.float32)
         scalar = torch.empty(1, device=x.device, dtype=torch.float32)
@@ -274,7 +275,8 @@ class VitEngine:
                 if lo < 0 or hi >= ref.shape[1]:
                     raise IndexError(f"{name} out of range: [{lo}, {hi}] for {ref.shape[1]} classes")
         ls = L.LossSpecC()
-        ls.loss_kind = {"l2": L.LOSS_L2, "ce": L.LOSS_CE, "dlr": L.LOSS_DLR, "dlr-targeted": L.LOSS_DLR_TARGETED}[loss_kind]
+        ls.loss_kind = {"l2": L.LOSS_L2, "ce": L.LOSS_CE, "dlr": L.LOSS_DLR, "dlr-targeted": L.LOSS_DLR_TARGETED,
+                        "logit-diff": L.LOSS_LOGIT_DIFF}[loss_kind]
         ls.reduction = {"mean": L.RED_MEAN, "none": L.RED_NONE}[reduction]
         ls.output_normalize = int(bool(output_normalize))
         ls.logit_scale = float(logit_scale)
