@@ -121,6 +121,52 @@ int rvlm_k_attn_causal_fwd_f32(const float* qkv, float* o, int B, int H, int S, 
 int rvlm_k_text_embed(const int32_t* tokens, const float* token_embedding, const float* positional_embedding, float* x, int32_t* eot,
                       uint32_t* flags, int N, int context, int active_len, int vocab, int W, rvlm_stream_t stream);
 
+/* The encoder's non-GEMM kernels, one entry per host launcher (tests/test_gpu_kernel_rows.py).  Row-major, contiguous rows
+ * (leading dimension = the row width) unless a leading dimension is passed. */
+/* LayerNorm kernels of the bf16 engine come in two forms: the row-register kernels (8 columns per lane and 512-column slab,
+ * W = 512 / 1024 / 1536 / 2048) and the generic one.  rvlm_k_layernorm_form: the form rvlm_k_layernorm_fwd_bf16 and
+ * rvlm_k_layernorm_bwd_bf16 run at width W (the dispatchers' own rule). */
+#define RVLM_LN_FORM_GENERIC 0
+#define RVLM_LN_FORM_ROW8 1
+int rvlm_k_layernorm_form(int W);
+int rvlm_k_layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd,
+                              int M, int W, rvlm_stream_t stream);
+/* split-bf16 ("x3") operand passes (csrc/x3_kernels.hip).  A3 [rows_out, 3K] = [hi | hi | lo] of A [M, K], rows M .. rows_out - 1
+ * zero; K % 8 == 0 */
+int rvlm_k_x3_split_rows(const float* A, long lda, uint16_t* A3, int M, int rows_out, int K, rvlm_stream_t stream);
+/* mode 0: act(h); mode 1: out * act'(h).  A3 == NULL: the fp32 result goes to out [M, N]; else to A3 [rows_out, 3N] = [hi | hi | lo]
+ * (out is then only read, in mode 1).  dact_bf (mode 0 only, optional): bf16(act'(h)), row stride ld_dact */
+int rvlm_k_x3_act(const float* h, long ldh, float* out, long ldo, uint16_t* A3, int M, int rows_out, int N, int act, int mode,
+                  uint16_t* dact_bf, long ld_dact, rvlm_stream_t stream);
+/* out = bf16(A) (dact 0) or bf16(act'(A)) (dact 1) */
+int rvlm_k_x3_export_bf16(const float* A, long lda, uint16_t* out, long ldo, int M, int N, int act, int dact, rvlm_stream_t stream);
+/* LayerNorm whose result is written as the split copy A3 [rows_out, 3W]; RVLM_ERR_UNSUPPORTED (nothing launched) unless
+ * W = 512 / 1024 / 1536 / 2048 */
+int rvlm_k_x3_layernorm_fwd(const float* x, const float* gamma, const float* beta, uint16_t* A3, float* mean, float* rstd, int M,
+                            int rows_out, int W, rvlm_stream_t stream);
+/* weight [rows, cols] -> nk3 [rows, 3 cols] = [hi | lo | hi], t3 [cols, 3 rows] = the same of the transpose */
+int rvlm_k_x3_prepare_weight(const float* src, int rows, int cols, uint16_t* nk3, uint16_t* t3, rvlm_stream_t stream);
+/* class-token attention of the last block on packed qkv [B*S, 3*64*H]: o [B, 64*H] (row b = image b's class token), lse [B*H]
+ * (natural log); bwd writes dqkv [B*S, 3*64*H] in full (dQ rows of the other tokens are zero) */
+int rvlm_k_attn_cls_fwd_bf16(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, rvlm_stream_t stream);
+int rvlm_k_attn_cls_bwd_bf16(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, uint16_t* dqkv, int B,
+                             int H, int S, rvlm_stream_t stream);
+/* tokens = [cls ; patch_out [B*(S-1), W]] + pos [S, W]; x0 [B*S, W] = ln_pre(tokens), mean / rstd [B*S]; tokens_out optional.
+ * bwd: d_patch [B*(S-1), W] (fp32, or bf16 with bf16_out) = the LayerNorm backward of the patch rows of dx0 */
+int rvlm_k_embed_lnpre_fwd(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta,
+                           float* x0, float* mean, float* rstd, float* tokens_out, int B, int S, int W, rvlm_stream_t stream);
+int rvlm_k_embed_lnpre_bwd(const float* dx0, const float* patch_out, const float* pos, const float* gamma, const float* mean,
+                           const float* rstd, void* d_patch, int bf16_out, int B, int S, int W, rvlm_stream_t stream);
+/* A0 [B*(img/P)^2, lda] (fp32, or bf16 with bf16_out): columns c*P*P + i*P + j = ((x (+ delta)) - mean_c) / std_c, columns
+ * 3*P*P .. Kpad-1 zero; mean3 / std3 are HOST arrays of 3.  col2im: grad_x [B, 3, img, img] = dA0[row, col] / std_c */
+int rvlm_k_im2col_normalize(const float* x, const float* delta, int B, int img, int P, const float* mean3, const float* std3,
+                            void* A0, long lda, int Kpad, int bf16_out, rvlm_stream_t stream);
+int rvlm_k_col2im_grad(const void* dA0, long lda, int bf16_in, int B, int img, int P, const float* std3, float* grad_x,
+                       rvlm_stream_t stream);
+/* backward of rvlm_l2_normalize_rows: d_raw = (d_out - ehat (ehat . d_out)) * inv_norm */
+int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, const float* inv_norm, float* d_raw, int B, int D,
+                            rvlm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

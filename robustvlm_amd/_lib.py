@@ -247,6 +247,28 @@ _SIGS.update({
     "rvlm_fab_jacobian_argmin": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, c_f32p, c_f32p,
                                            c_f32p, c_stream]),
 })
+_SIGS.update({
+    # the encoder's non-GEMM kernels (include/rvlm_kernels.h, tests/test_gpu_kernel_rows.py)
+    "rvlm_k_layernorm_form": (C.c_int, [C.c_int]),
+    "rvlm_k_layernorm_fwd_bf16": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_x3_split_rows": (C.c_int, [c_f32p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_x3_act": (C.c_int, [c_f32p, C.c_long, c_f32p, C.c_long, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.c_void_p, C.c_long, c_stream]),
+    "rvlm_k_x3_export_bf16": (C.c_int, [c_f32p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_x3_layernorm_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_x3_prepare_weight": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, c_stream]),
+    "rvlm_k_attn_cls_fwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_attn_cls_bwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_embed_lnpre_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int,
+                                         C.c_int, c_stream]),
+    "rvlm_k_embed_lnpre_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, c_stream]),
+    "rvlm_k_im2col_normalize": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          C.c_void_p, C.c_long, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_col2im_grad": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), c_f32p,
+                                     c_stream]),
+    "rvlm_k_l2_normalize_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

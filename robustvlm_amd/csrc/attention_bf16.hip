@@ -1285,6 +1285,7 @@ static int set_lds(K kernel, size_t bytes) {
 
 int attn_fwd_bf16(const bf16_t* qkv, long ldqkv, bf16_t* o, long ldo, float* lse, int B, int H,
                   int S, hipStream_t s) {
+    if (S > ATTN_BF16_MAX_S_FWD) return fail(RVLM_ERR_UNSUPPORTED, "attention: sequence too long for LDS-resident K/V");
     const int Sp = (int)round_up(S, 32), W = H * 64;
     const size_t lds_bytes = (size_t)Sp * 256;
     const float sl2 = 0.125f * 1.4426950408889634f;
@@ -1344,6 +1345,8 @@ int attn_fwd_bf16(const bf16_t* qkv, long ldqkv, bf16_t* o, long ldo, float* lse
 int attn_bwd_bf16(const bf16_t* qkv, long ldqkv, const bf16_t* o, long ldo, const bf16_t* d_o,
                   long lddo, const float* lse, float* dsum_scratch, bf16_t* dqkv, long lddqkv,
                   int B, int H, int S, hipStream_t s) {
+    // (both kernels' LDS requests are checked before the first one is enqueued)
+    if (S > ATTN_BF16_MAX_S_BWD) return fail(RVLM_ERR_UNSUPPORTED, "attention: sequence too long for the LDS-resident backward");
     const int Sp = (int)round_up(S, 32), W = H * 64;
     const float scale = 0.125f, sl2 = 0.125f * 1.4426950408889634f;
     const int nt = attn_block_threads(Sp / 32);

@@ -291,7 +291,7 @@ int linear_fwd<float>(rvlm_vit* h, hipStream_t s, const void* A, long lda, int M
         if (act) {
             // act(h) goes straight into the split copy the next linear (fc2: A = `out`, K = N) reads; `out` itself is not written
             // (its only other reader is the weight gradient, which this precision does not have)
-            const bool fuse = x3_takes(h, M, 256, N);
+            const bool fuse = x3_takes(h, M, K, N);      // fc2's own rule: [M, N] x [K, N]^T
             if ((rc = x3_act((const float*)g.out, ldo, (float*)out, ldo, fuse ? h->a3 : nullptr, M, (int)round_up(M, 256), N, h->cfg.act, 0, s,
                              h->cur_dact_out, ldo)))
                 return rc;
@@ -343,7 +343,7 @@ int linear_dgrad<float>(rvlm_vit* h, hipStream_t s, const void* dY, long lddy, i
         with_scratch(h, g);
         if ((rc = gemm_bf16_nt(g, s))) return rc;
         if (epi == EPI_BF16_DACT) {      // out * act'(h): straight into the split copy the next dgrad (fc1: dY = `out`) reads
-            const bool fuse = x3_takes(h, M, 256, K);
+            const bool fuse = x3_takes(h, M, N, K);      // the rule of fc1's dgrad: [M, K] x [N, K]^T
             if ((rc = x3_act((const float*)h_pre, ldo, (float*)out, ldo, fuse ? h->a3 : nullptr, M, (int)round_up(M, 256), K, h->cfg.act, 1, s)))
                 return rc;
             if (fuse) h->a3_of = out;
@@ -361,11 +361,12 @@ int linear_dgrad<float>(rvlm_vit* h, hipStream_t s, const void* dY, long lddy, i
 
 // x3 mode: the LayerNorm in front of a linear writes that linear's split operand itself (a3_of = the fp32 buffer the linear will be
 // handed, which is then never written: its only other reader is the weight gradient, which this precision does not have)
+// (false: not taken, the caller runs the LayerNorm kernel; true: *rc = the launch status)
 static bool ln_into_split(rvlm_vit* h, hipStream_t s, const float* x, const float* gamma, const float* beta, const void* ln_out,
-                          float* mean, float* rstd, int M, int N_next) {
+                          float* mean, float* rstd, int M, int N_next, int* rc) {
     if (!x3_takes(h, M, N_next, h->W)) return false;
-    if (!x3_layernorm_fwd(x, h->W, gamma, beta, h->a3, mean, rstd, M, (int)round_up(M, 256), h->W, s)) return false;
-    h->a3_of = ln_out;
+    if (!x3_layernorm_fwd(x, h->W, gamma, beta, h->a3, mean, rstd, M, (int)round_up(M, 256), h->W, s, rc)) return false;
+    if (*rc == RVLM_OK) h->a3_of = ln_out;
     return true;
 }
 
@@ -507,6 +508,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
     // xs / qkv / attn_o / lse, pooled, emb_raw, inv_norm): a non-saving pass therefore invalidates the saved forward
     // instead of letting a later backward run on a mixture of two passes.
     h->saved_B = 0;
+    h->a3_of = nullptr;      // (x3) nothing an earlier enqueue left in the split copy is this pass's operand
     // a forward FOR a peer (handoff) is a saving forward of an fp32-storage handle; it overwrites the peer's bf16 tensors
     // (sequence lengths the flash kernel does not take - S = 577 at 336 px - run the batched attention path as before: the handoff then
     // exports the bf16 tensors itself and takes the log-sum-exp rows the softmax pass wrote, vit_backward_from)
@@ -553,7 +555,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
         void* gact = save == 2 ? h->g_act_l[l] : h->g_act;
         {
             PROF("layernorm_fwd", 0, (double)M * W * (4 + sizeof(T)));
-            if (ln_into_split(h, s, x_in, y.ln1_w, y.ln1_b, ln1o, h->mean_at(1 + 2 * l), h->rstd_at(1 + 2 * l), M, 3 * W)) {}
+            if (ln_into_split(h, s, x_in, y.ln1_w, y.ln1_b, ln1o, h->mean_at(1 + 2 * l), h->rstd_at(1 + 2 * l), M, 3 * W, &rc)) { if (rc) return rc; }
             else
             if ((rc = layernorm_fwd<T>(x_in, W, y.ln1_w, y.ln1_b, (T*)ln1o, W, h->mean_at(1 + 2 * l),
                                        h->rstd_at(1 + 2 * l), M, W, s))) return rc;
@@ -599,7 +601,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
         }
         {
             PROF("layernorm_fwd", 0, (double)M * W * (4 + sizeof(T)));
-            if (ln_into_split(h, s, x_mid, y.ln2_w, y.ln2_b, ln2o, h->mean_at(2 + 2 * l), h->rstd_at(2 + 2 * l), M, 4 * W)) {}
+            if (ln_into_split(h, s, x_mid, y.ln2_w, y.ln2_b, ln2o, h->mean_at(2 + 2 * l), h->rstd_at(2 + 2 * l), M, 4 * W, &rc)) { if (rc) return rc; }
             else
             if ((rc = layernorm_fwd<T>(x_mid, W, y.ln2_w, y.ln2_b, (T*)ln2o, W, h->mean_at(2 + 2 * l),
                                        h->rstd_at(2 + 2 * l), M, W, s))) return rc;
@@ -664,6 +666,7 @@ static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, 
     // the fp32 residual-gradient stream, or none (LayerNorm backward then accumulates in the bf16 buffer, rvlm_vit::lp_dres)
     float* const dres32 = (LP && h->lp_dres && !fp32_dres) ? nullptr : h->dres;
     int rc;
+    h->a3_of = nullptr;
     {
         PROF("head_bwd", 2.0 * B * W * D, 0);
         const float* d_raw = d_emb;
@@ -1057,6 +1060,11 @@ extern "C" int rvlm_vit_create(const rvlm_vit_config* cfg, const rvlm_vit_weight
                  "precision (no weight gradients)");
     RVLM_REQUIRE(cfg->act == RVLM_ACT_QUICK_GELU || cfg->act == RVLM_ACT_GELU, "rvlm_vit_create: act");
     RVLM_REQUIRE(cfg->width <= 2048, "rvlm_vit_create: width > 2048 unsupported");
+    if (cfg->precision == RVLM_PREC_BF16) {      // the bf16 flash kernels' sequence limits (kernels.h), here instead of at the first step
+        const long g = cfg->image_size / cfg->patch, seq = g * g + 1;
+        if (seq > ATTN_BF16_MAX_S_FWD || (cfg->trainable >= 0 && seq > ATTN_BF16_MAX_S_BWD))
+            return fail(RVLM_ERR_UNSUPPORTED, "rvlm_vit_create: bf16 attention takes at most 640 tokens (608 with a backward)");
+    }
     hipStream_t s = (hipStream_t)stream;
     rvlm_vit* h = new rvlm_vit();
     static unsigned long long next_uid = 0;

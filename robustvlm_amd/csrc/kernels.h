@@ -83,6 +83,9 @@ int gemm_bf16_nt(const GemmBf16& p, hipStream_t s);
 template <typename TO>
 int layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, TO* y, long ldy,
                   float* mean, float* rstd, int M, int W, hipStream_t s);
+// widths the row-register forms take (layernorm_fwd8 with bf16 output, layernorm_bwd8 with bf16 dy / copy; leading dimensions
+// that are multiples of 8 elements): the dispatchers' rule, also what the test hook rvlm_k_layernorm_form reports
+bool layernorm_row8_covers(int W);
 // dres[m,:] (+)= LN'(dy[m,:]) ; optionally also writes dres as TB (A operand of the next dgrad GEMM)
 // accumulate=0 overwrites dres; accumulate=-S accumulates on rows that are multiples of S only (the other rows of
 // dres are overwritten: the class-token tail leaves a gradient on the class rows and garbage elsewhere).
@@ -136,6 +139,9 @@ int softmax_rows_bwd(const float* p, float* dp, long rows, int cols, int ld, flo
 // bf16 flash attention (head_dim 64), qkv packed [M, 3W] bf16 (q | k | v), tokens of image b at
 // rows b*S .. b*S+S-1.
 // ---------------------------------------------------------------------------------------------
+// Longest sequences: a workgroup's 160 KiB of LDS hold round_up(S, 32) rows of K and V in the forward (256 B per row) and of Q, dO,
+// lse2 and D in the dK / dV kernel with streamed K / V (264 B per row).  Longer sequences return RVLM_ERR_UNSUPPORTED with nothing enqueued.
+constexpr int ATTN_BF16_MAX_S_FWD = 160 * 1024 / 256, ATTN_BF16_MAX_S_BWD = 160 * 1024 / 264 / 32 * 32;
 int attn_fwd_bf16(const bf16_t* qkv, long ldqkv, bf16_t* o, long ldo, float* lse, int B, int H,
                   int S, hipStream_t s);
 int attn_bwd_bf16(const bf16_t* qkv, long ldqkv, const bf16_t* o, long ldo, const bf16_t* d_o,
@@ -180,8 +186,10 @@ size_t wgrad_slab_bytes(int N, int K);
 // split-bf16 ("x3") linears of the fp32-storage engine (x3_kernels.hip)
 int x3_split_rows(const float* A, long lda, bf16_t* A3, int M, int rows_out, int K, hipStream_t s);
 int x3_prepare_weight(const float* src, int rows, int cols, bf16_t* nk3, bf16_t* t3, hipStream_t s);
+// false: width not covered, nothing launched (the caller runs the fp32 LayerNorm and lets the linear split its output); true: *rc_out =
+// the launch status
 bool x3_layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, bf16_t* A3, float* mean, float* rstd, int M,
-                      int rows_out, int W, hipStream_t s);
+                      int rows_out, int W, hipStream_t s, int* rc_out);
 // dact_bf != null (mode 0 only): also writes bf16(act'(h)) there (row stride ld_dact) - the bf16 backward's stored derivative (handoff)
 int x3_act(const float* hbuf, long ldh, float* out, long ldo, bf16_t* A3, int M, int rows_out, int N, int act, int mode, hipStream_t s,
            bf16_t* dact_bf = nullptr, long ld_dact = 0);

@@ -386,3 +386,67 @@ extern "C" int rvlm_k_wgrad_bf16(const uint16_t* dY, long lddy, const uint16_t* 
     return rc;
 }
 extern "C" void rvlm_k_wgrad_set_transposed(int v) { g_wgrad_transposed = v; }
+
+// ---- the encoder's non-GEMM kernels, one hook per host launcher of kernels.h (tests/test_gpu_kernel_rows.py) ----
+extern "C" int rvlm_k_layernorm_form(int W) { return layernorm_row8_covers(W) ? RVLM_LN_FORM_ROW8 : RVLM_LN_FORM_GENERIC; }
+extern "C" int rvlm_k_layernorm_fwd_bf16(const float* x, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd,
+                                         int M, int W, rvlm_stream_t stream) {
+    return layernorm_fwd<bf16_t>(x, W, gamma, beta, (bf16_t*)y, W, mean, rstd, M, W, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_x3_split_rows(const float* A, long lda, uint16_t* A3, int M, int rows_out, int K, rvlm_stream_t stream) {
+    return x3_split_rows(A, lda, (bf16_t*)A3, M, rows_out, K, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_x3_act(const float* hbuf, long ldh, float* out, long ldo, uint16_t* A3, int M, int rows_out, int N, int act,
+                             int mode, uint16_t* dact_bf, long ld_dact, rvlm_stream_t stream) {
+    return x3_act(hbuf, ldh, out, ldo, (bf16_t*)A3, M, rows_out, N, act, mode, (hipStream_t)stream, (bf16_t*)dact_bf, ld_dact);
+}
+extern "C" int rvlm_k_x3_export_bf16(const float* A, long lda, uint16_t* out, long ldo, int M, int N, int act, int dact,
+                                     rvlm_stream_t stream) {
+    return x3_export_bf16(A, lda, (bf16_t*)out, ldo, M, N, act, dact, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_x3_layernorm_fwd(const float* x, const float* gamma, const float* beta, uint16_t* A3, float* mean, float* rstd,
+                                       int M, int rows_out, int W, rvlm_stream_t stream) {
+    int rc = RVLM_OK;
+    if (!x3_layernorm_fwd(x, W, gamma, beta, (bf16_t*)A3, mean, rstd, M, rows_out, W, (hipStream_t)stream, &rc))
+        return fail(RVLM_ERR_UNSUPPORTED, "rvlm_k_x3_layernorm_fwd: width not covered (W = 512, 1024, 1536, 2048)");
+    return rc;
+}
+extern "C" int rvlm_k_x3_prepare_weight(const float* src, int rows, int cols, uint16_t* nk3, uint16_t* t3, rvlm_stream_t stream) {
+    return x3_prepare_weight(src, rows, cols, (bf16_t*)nk3, (bf16_t*)t3, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_attn_cls_fwd_bf16(const uint16_t* qkv, uint16_t* o, float* lse, int B, int H, int S, rvlm_stream_t stream) {
+    return attn_cls_fwd_bf16((const bf16_t*)qkv, 3L * H * 64, (bf16_t*)o, H * 64L, lse, B, H, S, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_attn_cls_bwd_bf16(const uint16_t* qkv, const uint16_t* o, const uint16_t* d_o, const float* lse, uint16_t* dqkv,
+                                        int B, int H, int S, rvlm_stream_t stream) {
+    return attn_cls_bwd_bf16((const bf16_t*)qkv, 3L * H * 64, (const bf16_t*)o, H * 64L, (const bf16_t*)d_o, H * 64L, lse,
+                             (bf16_t*)dqkv, 3L * H * 64, B, H, S, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_embed_lnpre_fwd(const float* patch_out, const float* cls, const float* pos, const float* gamma, const float* beta,
+                                      float* x0, float* mean, float* rstd, float* tokens_out, int B, int S, int W, rvlm_stream_t stream) {
+    return embed_lnpre_fwd<float>(patch_out, W, cls, pos, gamma, beta, x0, W, mean, rstd, B, S, W, (hipStream_t)stream, tokens_out);
+}
+extern "C" int rvlm_k_embed_lnpre_bwd(const float* dx0, const float* patch_out, const float* pos, const float* gamma, const float* mean,
+                                      const float* rstd, void* d_patch, int bf16_out, int B, int S, int W, rvlm_stream_t stream) {
+    if (bf16_out)
+        return embed_lnpre_bwd<bf16_t>(dx0, W, patch_out, W, nullptr, pos, gamma, mean, rstd, (bf16_t*)d_patch, W, B, S, W, (hipStream_t)stream);
+    return embed_lnpre_bwd<float>(dx0, W, patch_out, W, nullptr, pos, gamma, mean, rstd, (float*)d_patch, W, B, S, W, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_im2col_normalize(const float* x, const float* delta, int B, int img, int P, const float* mean3, const float* std3,
+                                       void* A0, long lda, int Kpad, int bf16_out, rvlm_stream_t stream) {
+    if (!x || !A0 || !mean3 || !std3 || B <= 0 || P <= 0 || img % P != 0 || Kpad < 3 * P * P || lda < Kpad)
+        return fail(RVLM_ERR_ARG, "rvlm_k_im2col_normalize: bad arguments");
+    if (bf16_out) return im2col_normalize<bf16_t>(x, delta, B, img, P, mean3, std3, (bf16_t*)A0, lda, Kpad, (hipStream_t)stream);
+    return im2col_normalize<float>(x, delta, B, img, P, mean3, std3, (float*)A0, lda, Kpad, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_col2im_grad(const void* dA0, long lda, int bf16_in, int B, int img, int P, const float* std3, float* grad_x,
+                                  rvlm_stream_t stream) {
+    if (!dA0 || !std3 || !grad_x || B <= 0 || P <= 0 || img % P != 0 || lda < 3 * P * P)
+        return fail(RVLM_ERR_ARG, "rvlm_k_col2im_grad: bad arguments");
+    if (bf16_in) return col2im_grad<bf16_t>((const bf16_t*)dA0, lda, B, img, P, std3, grad_x, (hipStream_t)stream);
+    return col2im_grad<float>((const float*)dA0, lda, B, img, P, std3, grad_x, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, const float* inv_norm, float* d_raw, int B, int D,
+                                       rvlm_stream_t stream) {
+    return l2_normalize_bwd(d_out, e_raw, inv_norm, d_raw, B, D, (hipStream_t)stream);
+}

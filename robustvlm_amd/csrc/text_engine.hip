@@ -152,10 +152,10 @@ static int linear(rvlm_text* h, hipStream_t s, const void* A, long lda, int M, i
 // LayerNorm in front of a linear of N_next outputs: x3 writes that linear's split operand itself where the kernel covers the width
 static int ln_fwd(rvlm_text* h, hipStream_t s, const float* x, const float* gamma, const float* beta, int M, int N_next) {
     const int W = h->W;
-    if (t_x3_takes(h, M, N_next, W) && x3_layernorm_fwd(x, W, gamma, beta, h->a3, nullptr, nullptr, M, (int)round_up(M, 256), W, s)) {
-        RVLM_CHECK_LAUNCH();
-        h->a3_of = h->ln_out;
-        return RVLM_OK;
+    int rc = RVLM_OK;
+    if (t_x3_takes(h, M, N_next, W) && x3_layernorm_fwd(x, W, gamma, beta, h->a3, nullptr, nullptr, M, (int)round_up(M, 256), W, s, &rc)) {
+        if (rc == RVLM_OK) h->a3_of = h->ln_out;
+        return rc;
     }
     if (h->bf16) return layernorm_fwd<bf16_t>(x, W, gamma, beta, (bf16_t*)h->ln_out, W, nullptr, nullptr, M, W, s);
     return layernorm_fwd<float>(x, W, gamma, beta, (float*)h->ln_out, W, nullptr, nullptr, M, W, s);

@@ -107,6 +107,7 @@ layernorm_fwd8_kernel(const float* __restrict__ x, long ldx, const float* __rest
         *(bf16x8*)(yr + it * 512) = o;
     }
 }
+bool layernorm_row8_covers(int W) { return W > 0 && W % 512 == 0 && W <= 2048; }
 template <typename TO>
 static bool layernorm_fwd8(const float*, long, const float*, const float*, TO*, long, float*, float*, int, int, hipStream_t) {
     return false;
@@ -114,7 +115,7 @@ static bool layernorm_fwd8(const float*, long, const float*, const float*, TO*, 
 template <>
 bool layernorm_fwd8<bf16_t>(const float* x, long ldx, const float* gamma, const float* beta, bf16_t* y, long ldy,
                             float* mean, float* rstd, int M, int W, hipStream_t s) {
-    if (W % 512 != 0 || W > 2048 || ldx % 4 != 0 || ldy % 8 != 0) return false;
+    if (!layernorm_row8_covers(W) || ldx % 4 != 0 || ldy % 8 != 0) return false;
     const dim3 grid(cdiv(M, 4)), block(256);
     switch (W / 512) {
         case 1: hipLaunchKernelGGL((layernorm_fwd8_kernel<1>), grid, block, 0, s, x, ldx, gamma, beta, y, ldy, mean, rstd, M); break;
@@ -271,7 +272,7 @@ template <>
 bool layernorm_bwd8<bf16_t, bf16_t>(const bf16_t* dy, long lddy, const float* x, long ldx, const float* gamma,
                                     const float* mean, const float* rstd, float* dres, long lddres, bf16_t* dres_lp,
                                     long ldlp, int accumulate, int M, int W, hipStream_t s) {
-    if (W % 512 != 0 || W > 2048 || lddy % 8 != 0 || ldx % 4 != 0 || lddres % 4 != 0 || ldlp % 8 != 0) return false;
+    if (!layernorm_row8_covers(W) || lddy % 8 != 0 || ldx % 4 != 0 || lddres % 4 != 0 || ldlp % 8 != 0) return false;
     if (!dres && !dres_lp) return false;
     const dim3 grid(cdiv(M, 4)), block(256);
 #define RVLM_LNB8(NVV) do { if (dres) hipLaunchKernelGGL((layernorm_bwd8_kernel<NVV, false>), grid, block, 0, s, dy, lddy, x, ldx, gamma, mean, \

@@ -224,10 +224,14 @@ x3_layernorm_fwd_kernel(const float* __restrict__ x, long ldx, const float* __re
         *(bf16x8*)(o + it * 512) = hi; *(bf16x8*)(o + it * 512 + W) = hi; *(bf16x8*)(o + it * 512 + 2 * W) = lo;
     }
 }
-// false: width not covered (the caller runs the fp32 LayerNorm and lets the linear split its output)
+static int check_launch() {
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+// false: width not covered, nothing launched (the caller runs the fp32 LayerNorm and lets the linear split its output)
 bool x3_layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, bf16_t* A3, float* mean, float* rstd, int M,
-                      int rows_out, int W, hipStream_t s) {
-    if (W % 512 != 0 || W > 2048 || ldx % 4 != 0) return false;
+                      int rows_out, int W, hipStream_t s, int* rc_out) {
+    if (W <= 0 || W % 512 != 0 || W > 2048 || ldx % 4 != 0) return false;
     const dim3 grid(cdiv(rows_out, 4)), block(256);
     switch (W / 512) {
         case 1: hipLaunchKernelGGL((x3_layernorm_fwd_kernel<1>), grid, block, 0, s, x, ldx, gamma, beta, A3, mean, rstd, M, rows_out); break;
@@ -235,6 +239,7 @@ bool x3_layernorm_fwd(const float* x, long ldx, const float* gamma, const float*
         case 3: hipLaunchKernelGGL((x3_layernorm_fwd_kernel<3>), grid, block, 0, s, x, ldx, gamma, beta, A3, mean, rstd, M, rows_out); break;
         default: hipLaunchKernelGGL((x3_layernorm_fwd_kernel<4>), grid, block, 0, s, x, ldx, gamma, beta, A3, mean, rstd, M, rows_out); break;
     }
+    *rc_out = check_launch();
     return true;
 }
 

@@ -102,3 +102,27 @@ def attn_ref(qkv, B, H, S):
     s = (q @ k.transpose(-1, -2)) * 0.125
     o = torch.softmax(s, -1) @ v
     return o.permute(0, 2, 1, 3).reshape(B * S, W)
+
+
+def row_rel_l2(got, ref):
+    """Relative L2 error of every row (the last dimension) in fp64.  The rows of one group (the second-to-last dimension: the tokens of
+    one (image, head) for attention, all rows of a matrix otherwise) share a floor: a row's error norm is divided by max(its reference
+    norm, 0.05 x the group's median row norm), so that rows whose true value is nearly zero (keys nobody attends to under a peaked
+    softmax) are judged on an absolute scale instead of being exempted or made to flake."""
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    err = (got - ref).norm(dim=-1)
+    nrm = ref.norm(dim=-1)
+    floor = 0.05 * nrm.median(dim=-1, keepdim=True).values
+    return err / torch.maximum(nrm, floor).clamp_min(1e-300)
+
+
+def assert_rows(name, got, ref, bar, dims=("b", "h", "row")):
+    """Every row of ``got`` within ``bar`` of ``ref`` (row_rel_l2); the message names the worst row.  Returns the worst value."""
+    e = row_rel_l2(got, ref)
+    flat = int(torch.nan_to_num(e, nan=float("inf")).argmax())          # a NaN row is the worst row
+    idx = np.unravel_index(flat, tuple(e.shape))
+    worst = float(e.flatten()[flat])
+    where = ", ".join(f"{n} {i}" for n, i in zip(dims[len(dims) - len(idx):], idx))
+    assert worst <= bar, f"{name}: worst row ({where}) has relative L2 error {worst:.3e} > {bar:.1e}"
+    return worst
