@@ -31,6 +31,9 @@ extern "C" {
 #define RVLM_HAS_TEXT 1
 /* RVLM_HAS_FAB: the rvlm_fab_* entry points (FAB / FAB-T, L-inf), RVLM_LOSS_LOGIT_DIFF and RVLM_FLAG_FAB_NONFINITE */
 #define RVLM_HAS_FAB 1
+/* RVLM_HAS_INPUT_RESIZE: rvlm_vit_set_input_size (bicubic up-sampling as part of the model), rvlm_resize_bicubic(_adjoint),
+ * rvlm_resize_taps */
+#define RVLM_HAS_INPUT_RESIZE 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -152,6 +155,31 @@ int rvlm_vit_forward_for(rvlm_vit* h, rvlm_vit* consumer, const float* x, const 
  * forwards agree bit for bit, which FARE's zero gradient at delta = 0 relies on; switch it on for the handle whose saving forwards
  * are all rvlm_vit_forward_for, so that its clean embedding and its first-iteration embedding share one arithmetic).  ABI 109. */
 int rvlm_vit_set_flash_inference(rvlm_vit* h, int on);
+
+/* ---------------------------------------------------------------------------------------------
+ * Bicubic resize inside the model (RVLM_HAS_INPUT_RESIZE): ClassificationModel(..., resizer=Resize(224, BICUBIC,
+ * antialias=False)) of CLIP_eval/clip_robustbench.py:60-68,104-114 - the attack's images, perturbation and eps ball live at the
+ * dataset's own resolution and the input gradient comes back through the resize.
+ * The operator is torch.nn.functional.interpolate(x, (out_h, out_w), mode='bicubic', align_corners=False, antialias=False) on
+ * float tensors: Y = R_h X R_w^T with, per output index o, src = (in / out) (o + 0.5) - 0.5, i = floor(src), t = src - i, four taps
+ * i-1 .. i+2 (index clamped to [0, in-1]), cubic-convolution weights with A = -0.75 (computed in double, rounded to fp32).  The result
+ * is not clamped.
+ * ------------------------------------------------------------------------------------------- */
+/* Handle state.  (image_size, image_size) or (0, 0): the model's own resolution, the default.  Otherwise every entry that takes or
+ * returns images (rvlm_vit_forward, rvlm_vit_backward_input, rvlm_vit_fwd_inputgrad, rvlm_pgd_run*, rvlm_apgd_run*) reads / writes
+ * [B, 3, in_h, in_w]: x (+ delta) is resized to (image_size, image_size) inside the patch embedding, grad_x is the adjoint's.
+ * 1 <= in_h, in_w <= image_size (up-sampling); larger, or a trainable handle: RVLM_ERR_UNSUPPORTED.  Changing the size invalidates a
+ * saved forward (a backward then returns RVLM_ERR_STATE).  The two-handle entries (rvlm_pgd_run_mixed*, rvlm_vit_forward_for,
+ * rvlm_vit_backward_input_from) need the same size on both handles, else RVLM_ERR_STATE.  First use of a size on a device builds
+ * its tap tables (a synchronous copy of a few KB). */
+int rvlm_vit_set_input_size(rvlm_vit* h, int in_h, int in_w);
+/* Standalone: y [planes, out_h, out_w] <- x [planes, in_h, in_w] and the adjoint gx [planes, in_h, in_w] <- gy [planes, out_h, out_w]
+ * (gx = R_h^T gy R_w), any pair of sizes in 1..32768.  The adjoint is a gather in a fixed order: no atomics, bit-reproducible. */
+int rvlm_resize_bicubic(const float* x, long planes, int in_h, int in_w, int out_h, int out_w, float* y, rvlm_stream_t stream);
+int rvlm_resize_bicubic_adjoint(const float* gy, long planes, int in_h, int in_w, int out_h, int out_w, float* gx,
+                                rvlm_stream_t stream);
+/* HOST: the tap table of one axis, idx [out, 4] (clamped) and w [out, 4]; needs no device. */
+int rvlm_resize_taps(int in, int out, int32_t* idx, float* w);
 
 /* Weight gradients of the outer training step (loss_total.backward(), …clip.py:361): for the last
  * forward run with save_for_backward == 2 on a `trainable` handle, writes (accumulate == 0) or adds
@@ -493,7 +521,8 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * 107: rvlm_l2_random_start; 108: RVLM_PREC_F32X3 (split-bf16 linears over fp32 storage);
                            * 109: rvlm_vit_backward_input_from, rvlm_vit_forward_for, rvlm_vit_set_flash_inference, rvlm_pgd_run_mixed_fwd (fp32-storage forward, bf16 backward);
                            * still 109, additions only: rvlm_text_* (CLIP text tower, forward only, announced by RVLM_HAS_TEXT);
-                           * rvlm_fab_* (FAB / FAB-T L-inf), RVLM_LOSS_LOGIT_DIFF, RVLM_FLAG_FAB_NONFINITE (announced by RVLM_HAS_FAB) */
+                           * rvlm_fab_* (FAB / FAB-T L-inf), RVLM_LOSS_LOGIT_DIFF, RVLM_FLAG_FAB_NONFINITE (announced by RVLM_HAS_FAB);
+                           * rvlm_vit_set_input_size, rvlm_resize_bicubic(_adjoint), rvlm_resize_taps (announced by RVLM_HAS_INPUT_RESIZE) */
 
 #ifdef __cplusplus
 }

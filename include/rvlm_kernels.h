@@ -163,6 +163,13 @@ int rvlm_k_im2col_normalize(const float* x, const float* delta, int B, int img, 
                             void* A0, long lda, int Kpad, int bf16_out, rvlm_stream_t stream);
 int rvlm_k_col2im_grad(const void* dA0, long lda, int bf16_in, int B, int img, int P, const float* std3, float* grad_x,
                        rvlm_stream_t stream);
+/* The same two with a bicubic resize (rvlm.h, RVLM_HAS_INPUT_RESIZE) between the image and the patches: x / delta / grad_x are
+ * [B, 3, in_h, in_w], the patches those of the (img, img) image; delta is added before the resize; 1 / std is applied once per
+ * low-resolution pixel. */
+int rvlm_k_resize_im2col_normalize(const float* x, const float* delta, int B, int in_h, int in_w, int img, int P, const float* mean3,
+                                   const float* std3, void* A0, long lda, int Kpad, int bf16_out, rvlm_stream_t stream);
+int rvlm_k_col2im_resize_grad(const void* dA0, long lda, int bf16_in, int B, int in_h, int in_w, int img, int P, const float* std3,
+                              float* grad_x, rvlm_stream_t stream);
 /* backward of rvlm_l2_normalize_rows: d_raw = (d_out - ehat (ehat . d_out)) * inv_norm */
 int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, const float* inv_norm, float* d_raw, int B, int D,
                             rvlm_stream_t stream);

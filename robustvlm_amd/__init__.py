@@ -12,6 +12,7 @@ arithmetic op runs in the in-tree HIP library ``librvlm.so`` (include/rvlm.h):
     train/adversarial_training_clip.py::ClipVisionModel robustvlm_amd.ClipVisionModel
       ::ComputeLossWrapper/compute_loss/l2/ce           robustvlm_amd.{ComputeLossWrapper,...}
     CLIP_eval/clip_robustbench.py::ClassificationModel  robustvlm_amd.ClassificationModel
+    torchvision Resize(224, BICUBIC, antialias=False)   robustvlm_amd.BicubicResize  (the resizer= of the line above)
     open_clip VisionTransformer (third party)           robustvlm_amd.VitEngine
     open_clip CLIP.encode_text (third party)            robustvlm_amd.{TextEngine,ClipTextModel}
     CLIP_eval/eval_utils.py::get_text_embeddings        robustvlm_amd.get_text_embeddings
@@ -31,6 +32,7 @@ from .square import SquareAttack
 from .fab import FABAttack
 from .eval_utils import compute_accuracy_no_dataloader, zeroshot_head, get_text_embeddings, get_text_embeddings_ensemble
 from .preprocess import ResizeCenterCropToTensor
+from .resize import BicubicResize
 from .checkpoint import load_visual_state_dict, load_text_state_dict, CheckpointWriter, resume_paths
 
 __all__ = ["VitConfig", "CONFIGS", "CLIP_MEAN", "CLIP_STD", "random_state_dict", "state_dict_shapes",
@@ -38,4 +40,4 @@ __all__ = ["VitConfig", "CONFIGS", "CLIP_MEAN", "CLIP_STD", "random_state_dict",
            "l2", "ce", "compute_acc", "project_perturbation", "normalize_grad", "pgd", "apgd_train",
            "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "FABAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths",
            "TextConfig", "TEXT_CONFIGS", "text_state_dict_shapes", "random_text_state_dict", "TextEngine", "ClipTextModel",
-           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict"]
+           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict", "BicubicResize"]

@@ -269,6 +269,17 @@ _SIGS.update({
                                      c_stream]),
     "rvlm_k_l2_normalize_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, c_stream]),
 })
+_SIGS.update({
+    # bicubic resize inside the model (csrc/resize_kernels.hip; RVLM_HAS_INPUT_RESIZE)
+    "rvlm_vit_set_input_size": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "rvlm_resize_bicubic": (C.c_int, [c_f32p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "rvlm_resize_bicubic_adjoint": (C.c_int, [c_f32p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_stream]),
+    "rvlm_resize_taps": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
+    "rvlm_k_resize_im2col_normalize": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float),
+                                                 C.POINTER(C.c_float), C.c_void_p, C.c_long, C.c_int, C.c_int, c_stream]),
+    "rvlm_k_col2im_resize_grad": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.POINTER(C.c_float), c_f32p, c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

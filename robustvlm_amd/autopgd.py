@@ -93,6 +93,25 @@ class APGDAttack():
         zt = x.gather(1, self.y_target.view(-1, 1)).squeeze(1)
         return -(zy - zt) / (top[:, 0] - .5 * (top[:, 2] + top[:, 3]) + 1e-12)
 
+    def _device_run(self, m, x, y, start, step0):
+        """rvlm_apgd_run with the zero-shot head and the loss on the device.  Every quantity of the attack is per sample: batches
+        beyond the engine's workspace (AutoAttack's bs = 250 on a max_batch = 128 engine) run as chunks of the device loop
+        (chunks of >= 2 images: the losses need batch > 1)."""
+        B, mb = x.shape[0], m.model.max_batch
+        bounds = list(range(0, B, mb)) + [B]
+        if len(bounds) > 2 and bounds[-1] - bounds[-2] < 2:
+            bounds[-2] -= 1
+        yt = self.y_target if self.loss == 'dlr-targeted' else None
+        parts = []
+        for lo, hi in zip(bounds[:-1], bounds[1:]):
+            parts.append(m.model.apgd_run(
+                x[lo:hi], None if start is None else start[lo:hi], self.loss, m.text_embedding, y[lo:hi], True,
+                self.eps, self.n_iter, step0, train_variant=False, logits_from_head=True,
+                logit_scale=m.logit_scale_value, want_extra=True, y_target=None if yt is None else yt[lo:hi],
+                rho=self.thr_decr, norm_kind=self._norm_kind))
+        x_best_adv, x_best, loss_best, acc = (torch.cat([p[i] for p in parts]) for i in range(4))
+        return x_best, acc.bool(), loss_best, x_best_adv
+
     def attack_single_run(self, x, y, x_init=None):
         """Returns (x_best, acc, loss_best, x_best_adv) like autopgd_base.py:205-451."""
         if self.loss not in ('ce', 'dlr', 'dlr-targeted'):
@@ -104,23 +123,11 @@ class APGDAttack():
         alpha = 2. if self.alpha is None else self.alpha                    # :296-299
         step0 = alpha * self.eps
         m = self.model
-        if isinstance(m, ClassificationModel) and x.shape[0] > 1 and m.logit_scale and m._identity_resizer:
-            # every quantity of the attack is per sample: batches beyond the engine's workspace (AutoAttack's bs = 250 on
-            # a max_batch = 128 engine) run as chunks of the device loop (chunks of >= 2 images: the losses need batch > 1)
-            B, mb = x.shape[0], m.model.max_batch
-            bounds = list(range(0, B, mb)) + [B]
-            if len(bounds) > 2 and bounds[-1] - bounds[-2] < 2:
-                bounds[-2] -= 1
-            yt = self.y_target if self.loss == 'dlr-targeted' else None
-            parts = []
-            for lo, hi in zip(bounds[:-1], bounds[1:]):
-                parts.append(m.model.apgd_run(
-                    x[lo:hi], None if start is None else start[lo:hi], self.loss, m.text_embedding, y[lo:hi], True,
-                    self.eps, self.n_iter, step0, train_variant=False, logits_from_head=True,
-                    logit_scale=m.logit_scale_value, want_extra=True, y_target=None if yt is None else yt[lo:hi],
-                    rho=self.thr_decr, norm_kind=self._norm_kind))
-            x_best_adv, x_best, loss_best, acc = (torch.cat([p[i] for p in parts]) for i in range(4))
-            return x_best, acc.bool(), loss_best, x_best_adv
+        if isinstance(m, ClassificationModel) and x.shape[0] > 1 and m.logit_scale:
+            # the resizer is the identity, or a BicubicResize the engine runs itself: the loop then works at x's own resolution
+            with m.engine_route(x) as on_device:
+                if on_device:
+                    return self._device_run(m, x, y, start, step0)
         if self.loss == 'ce':
             # nn.CrossEntropyLoss(reduction='none') (autopgd_base.py:249) on rvlm_ce_logits: unlike the trainer's ce() it
             # has no batch > 1 assert - a restart can be left with ONE robust point (autopgd_base.py:494-500)

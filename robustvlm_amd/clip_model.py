@@ -14,10 +14,13 @@ differentiate through it), the losses go through rvlm_loss_grad.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import _lib as L
 from .engine import VitEngine, _require_cuda, _f32c
+from .resize import BicubicResize
 from .text_engine import TextEngine
 
 
@@ -250,7 +253,11 @@ class _HeadLogitsFn(torch.autograd.Function):
 
 class ClassificationModel(torch.nn.Module):
     """Zero-shot head on the native encoder (CLIP_eval/clip_robustbench.py:50-69):
-    logits = normalize(encode_image(Normalize(resizer(x)))) @ T  [* exp(logit_scale) = 100]."""
+    logits = normalize(encode_image(Normalize(resizer(x)))) @ T  [* exp(logit_scale) = 100].
+
+    ``resizer``: None, a :class:`BicubicResize` (the reference's ``Resize(224, BICUBIC, antialias=False)``: where its result is
+    the engine's own resolution it runs INSIDE the engine - fused into the patch embedding, and the device attack loops work
+    at the input's resolution), or any other callable (applied as given; the attacks then take their generic route)."""
 
     def __init__(self, model, text_embedding, args=None, input_normalize=None, resizer=None,
                  logit_scale=True, logit_scale_value: float = 100.0):
@@ -265,6 +272,32 @@ class ClassificationModel(torch.nn.Module):
         self.logit_scale = logit_scale
         self.logit_scale_value = float(logit_scale_value)
 
+    def engine_input_size(self, vision):
+        """(h, w) if the engine itself can run this model's resizer on ``vision`` (``VitEngine.set_input_size``): a
+        :class:`BicubicResize` that takes ``vision``'s size, not above the model's, to exactly (image_size, image_size).
+        None otherwise - the identity resizer included."""
+        if not isinstance(self.resizer, BicubicResize) or not isinstance(vision, torch.Tensor) or vision.dim() != 4:
+            return None
+        h, w = int(vision.shape[-2]), int(vision.shape[-1])
+        img = self.model.cfg.image_size
+        if vision.shape[1] != 3 or vision.dtype != torch.float32 or max(h, w) > img or self.model.trainable:
+            return None
+        if self.resizer.output_size(h, w) != (img, img):
+            return None
+        return h, w
+
+    @contextlib.contextmanager
+    def engine_route(self, vision):
+        """For the device attack loops: yields True if they can take ``vision`` as it is - the resizer is the identity, or the
+        engine runs it (the handle's input size is then set for the duration of the block and restored after, exceptions
+        included) - and False for any other resizer."""
+        fused = self.engine_input_size(vision)
+        if fused is None:
+            yield self._identity_resizer
+        else:
+            with self.model.input_size_of(*fused):
+                yield True
+
     def forward(self, vision, output_normalize=True):
         assert output_normalize
         mb = self.model.max_batch
@@ -273,7 +306,13 @@ class ClassificationModel(torch.nn.Module):
             # are encoded in chunks; a differentiable call must fit (one saved forward per engine).  Chunks are cut
             # BEFORE the resizer so that each image passes through it exactly once
             return torch.cat([self.forward(vision[i:i + mb]) for i in range(0, vision.shape[0], mb)], 0)
-        vision = self.resizer(vision)
-        embedding_norm_ = self.vision(vision, True)
+        fused = self.engine_input_size(vision)
+        if fused is not None and not (torch.is_grad_enabled() and vision.requires_grad):
+            # prediction passes (Square, FAB, AutoAttack's clean pass): the engine's fused front end, nothing kept
+            with self.model.input_size_of(*fused):
+                embedding_norm_ = self.vision(vision, True)
+        else:
+            vision = self.resizer(vision)
+            embedding_norm_ = self.vision(vision, True)
         return _HeadLogitsFn.apply(embedding_norm_, self.text_embedding,
                                    self.logit_scale_value if self.logit_scale else 1.0)

@@ -108,8 +108,13 @@ struct rvlm_vit {
                                // (conv1, widths that are no multiple of 256, fewer than 256 tokens); t_elems elements each
     long Mpt = 0;
     size_t t_elems = 0;        // bf16 elements of tA (= of tB)
+    // Input size (rvlm_vit_set_input_size): images and perturbations are [B, 3, in_h, in_w]; where that is not (img, img) the
+    // bicubic resize to (img, img) is part of the model, fused into the patch embedding both ways (resize_kernels.hip).
+    int in_h = 0, in_w = 0;    // = img when no resize is active
+    bool resize = false;
+    ResizeAxis rs_h, rs_w;     // device tables of (in_h -> img), (in_w -> img) while `resize`
     // attack state
-    float* img_buf[5];         // [maxB*3*img*img]
+    float* img_buf[5];         // [maxB*3*img*img] (covers every input size up to the model's own)
     float *emb, *d_emb, *loss_ps, *loss_scalar, *loss_scratch;
     float *ap_loss_steps, *ap_loss_best, *ap_loss_best_lc, *ap_reduced_lc, *ap_step;
     uint8_t *ap_acc, *ap_pred, *ap_f0, *ap_f1, *ap_f2;
@@ -522,8 +527,11 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
     h->exported_to = 0; h->exported_dact = false;
     h->cur_qkv_bf = h->cur_o_bf = nullptr; h->cur_dact_out = nullptr;
     {
-        PROF("patch_im2col", 0, (double)B * 3 * h->img * h->img * (delta ? 8 : 4) + (double)M0 * h->Kpad * sizeof(T));
-        if ((rc = im2col_normalize<T>(x, delta, B, h->img, h->P, h->cfg.mean, h->cfg.std, (T*)h->A0, h->Kpad, h->Kpad, s))) return rc;
+        PROF("patch_im2col", 0, (double)B * 3 * h->in_h * h->in_w * (delta ? 8 : 4) + (double)M0 * h->Kpad * sizeof(T));
+        rc = h->resize ? resize_im2col_normalize<T>(x, delta, B, h->rs_h, h->rs_w, h->P, h->cfg.mean, h->cfg.std, (T*)h->A0, h->Kpad,
+                                                    h->Kpad, s)
+                       : im2col_normalize<T>(x, delta, B, h->img, h->P, h->cfg.mean, h->cfg.std, (T*)h->A0, h->Kpad, h->Kpad, s);
+        if (rc) return rc;
     }
     {
         PROF("gemm_patch_fwd", 2.0 * M0 * W * h->Kp, 0);
@@ -782,8 +790,10 @@ static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, 
         if (rc) return rc;
     }
     {
-        PROF("patch_col2im", 0, (double)B * 3 * h->img * h->img * 8);
-        if ((rc = col2im_grad<float>(h->dA0, h->Kpad, B, h->img, h->P, h->cfg.std, grad_x, s))) return rc;
+        PROF("patch_col2im", 0, (double)B * 3 * h->img * h->img * 4 + (double)B * 3 * h->in_h * h->in_w * 4);
+        rc = h->resize ? col2im_resize_grad<float>(h->dA0, h->Kpad, B, h->rs_h, h->rs_w, h->P, h->cfg.std, grad_x, s)
+                       : col2im_grad<float>(h->dA0, h->Kpad, B, h->img, h->P, h->cfg.std, grad_x, s);
+        if (rc) return rc;
     }
     return RVLM_OK;
 }
@@ -1073,7 +1083,7 @@ extern "C" int rvlm_vit_create(const rvlm_vit_config* cfg, const rvlm_vit_weight
     h->bf16 = cfg->precision == RVLM_PREC_BF16;
     h->x3 = cfg->precision == RVLM_PREC_F32X3;
     h->esz = h->bf16 ? 2 : 4;
-    h->img = cfg->image_size; h->P = cfg->patch; h->G = h->img / h->P; h->S = h->G * h->G + 1;
+    h->img = h->in_h = h->in_w = cfg->image_size; h->P = cfg->patch; h->G = h->img / h->P; h->S = h->G * h->G + 1;
     h->W = cfg->width; h->L = cfg->layers; h->H = cfg->heads; h->D = cfg->out_dim;
     h->Kp = 3 * h->P * h->P; h->Kpad = (int)round_up(h->Kp, 64);
     h->maxB = cfg->max_batch;
@@ -1255,6 +1265,34 @@ extern "C" int rvlm_vit_backward_input(rvlm_vit* h, const float* d_emb, int B, f
     return vit_backward(h, d_emb, B, grad_x, (hipStream_t)stream);
 }
 
+extern "C" int rvlm_vit_set_input_size(rvlm_vit* h, int in_h, int in_w) {
+    RVLM_REQUIRE(h, "rvlm_vit_set_input_size: null handle");
+    if (in_h == 0 && in_w == 0) in_h = in_w = h->img;
+    RVLM_REQUIRE(in_h >= 1 && in_w >= 1, "rvlm_vit_set_input_size: sizes must be positive ((0, 0) = the model's own)");
+    if (in_h > h->img || in_w > h->img)
+        return fail(RVLM_ERR_UNSUPPORTED, "rvlm_vit_set_input_size: inputs larger than image_size (down-sampling inside the engine)");
+    const bool resize = in_h != h->img || in_w != h->img;
+    if (resize && h->trainable)
+        return fail(RVLM_ERR_UNSUPPORTED, "rvlm_vit_set_input_size: a trainable handle runs at the model's own resolution only");
+    if (in_h == h->in_h && in_w == h->in_w) return RVLM_OK;
+    ResizeAxis ah, aw;
+    if (resize) {
+        int rc;
+        if ((rc = resize_axis_device(in_h, h->img, &ah))) return rc;
+        if ((rc = resize_axis_device(in_w, h->img, &aw))) return rc;
+    }
+    h->rs_h = ah; h->rs_w = aw;
+    h->in_h = in_h; h->in_w = in_w; h->resize = resize;
+    h->saved_B = 0;      // a forward saved at another geometry is not this size's to differentiate
+    return RVLM_OK;
+}
+
+static bool same_input_size(const rvlm_vit* a, const rvlm_vit* b) { return a->in_h == b->in_h && a->in_w == b->in_w; }
+#define RVLM_REQUIRE_SAME_INPUT(a, b, who)                                                                                   \
+    do {                                                                                                                      \
+        if (!same_input_size(a, b)) return fail(RVLM_ERR_STATE, who ": the two handles are set to different input sizes");   \
+    } while (0)
+
 extern "C" int rvlm_vit_set_flash_inference(rvlm_vit* h, int on) {
     RVLM_REQUIRE(h, "rvlm_vit_set_flash_inference: null handle");
     h->flash_inference = on != 0 && !h->bf16;
@@ -1268,6 +1306,7 @@ extern "C" int rvlm_vit_forward_for(rvlm_vit* h, rvlm_vit* consumer, const float
     RVLM_REQUIRE(!h->bf16 && consumer->bf16 && !h->inference_only && !consumer->inference_only && h->Mp == consumer->Mp &&
                  h->W == consumer->W && h->L == consumer->L && h->S == consumer->S && h->H == consumer->H,
                  "rvlm_vit_forward_for: needs an fp32-storage handle and a bf16 handle of the same architecture and max_batch");
+    RVLM_REQUIRE_SAME_INPUT(h, consumer, "rvlm_vit_forward_for");
     h->peer = consumer;
     const int rc = vit_forward(h, x, delta, B, output_normalize, 1, out_emb, (hipStream_t)stream);
     h->peer = nullptr;
@@ -1277,6 +1316,7 @@ extern "C" int rvlm_vit_forward_for(rvlm_vit* h, rvlm_vit* consumer, const float
 extern "C" int rvlm_vit_backward_input_from(rvlm_vit* h, rvlm_vit* h_saved, const float* d_emb, int B, float* grad_x,
                                             rvlm_stream_t stream) {
     RVLM_REQUIRE(h && h_saved && d_emb && grad_x, "rvlm_vit_backward_input_from: null argument");
+    RVLM_REQUIRE_SAME_INPUT(h, h_saved, "rvlm_vit_backward_input_from");
     return vit_backward_from(h, h_saved, d_emb, B, grad_x, (hipStream_t)stream);
 }
 
@@ -1354,7 +1394,7 @@ static int pgd_run_impl(rvlm_vit* h, rvlm_vit* hf, int n_first, const float* x, 
                         const rvlm_loss_spec* loss, int norm_kind, float eps, int iterations, float stepsize,
                         float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags, hipStream_t s,
                         bool handoff = false) {
-    const size_t n = (size_t)B * 3 * h->img * h->img;
+    const size_t n = (size_t)B * 3 * h->in_h * h->in_w;
     float *delta = h->img_buf[0], *vel = h->img_buf[1], *grad = h->img_buf[2];
     int rc;
     if (flags && (rc = rvlm_check_image_range(x, n, flags, s))) return rc;
@@ -1415,6 +1455,7 @@ extern "C" int rvlm_pgd_run_mixed(rvlm_vit* h, rvlm_vit* h_first, int n_first, c
                  h->H == h_first->H && h->D == h_first->D && h->cfg.act == h_first->cfg.act,
                  "rvlm_pgd_run_mixed: the two handles must hold the same architecture");
     RVLM_REQUIRE(!h->inference_only && !h_first->inference_only, "rvlm_pgd_run_mixed: inference-only handle");
+    RVLM_REQUIRE_SAME_INPUT(h, h_first, "rvlm_pgd_run_mixed");
     return pgd_run_impl(h, h_first, n_first, x, delta0, B, loss, norm_kind, eps, iterations, stepsize, momentum, mode_max,
                         x_adv_out, loss_trace, flags, (hipStream_t)stream);
 }
@@ -1433,6 +1474,7 @@ extern "C" int rvlm_pgd_run_mixed_fwd(rvlm_vit* h, rvlm_vit* h_first, int n_firs
     RVLM_REQUIRE(h->bf16 && !h_first->bf16, "rvlm_pgd_run_mixed_fwd: h must be a bf16 handle, h_first an fp32-storage (fp32 / x3) one");
     RVLM_REQUIRE(h->Mp == h_first->Mp && h->Mp0 == h_first->Mp0, "rvlm_pgd_run_mixed_fwd: the two handles need the same max_batch");
     RVLM_REQUIRE(!h->inference_only && !h_first->inference_only, "rvlm_pgd_run_mixed_fwd: inference-only handle");
+    RVLM_REQUIRE_SAME_INPUT(h, h_first, "rvlm_pgd_run_mixed_fwd");
     return pgd_run_impl(h, h_first, n_first, x, delta0, B, loss, norm_kind, eps, iterations, stepsize, momentum, mode_max,
                         x_adv_out, loss_trace, flags, (hipStream_t)stream, true);
 }
@@ -1458,7 +1500,7 @@ extern "C" int rvlm_apgd_run_norm(rvlm_vit* h, const float* x, const float* x_in
     RVLM_REQUIRE(loss->loss_kind == RVLM_LOSS_L2 || loss->loss_kind == RVLM_LOSS_CE || logits_from_head,
                  "rvlm_apgd_run: the DLR losses run on the classification head (logits_from_head = 1)");
     hipStream_t s = (hipStream_t)stream;
-    const size_t npix = (size_t)3 * h->img * h->img, n = npix * B;
+    const size_t npix = (size_t)3 * h->in_h * h->in_w, n = npix * B;
     float *x_adv = h->img_buf[0], *x_adv_old = h->img_buf[1], *x_best = h->img_buf[2], *grad = h->img_buf[3],
           *grad_best = h->img_buf[4];
     int rc;

@@ -106,6 +106,32 @@ int im2col_normalize(const float* x, const float* delta, int B, int img, int P, 
 template <typename T>
 int col2im_grad(const T* dA0, long lda, int B, int img, int P, const float* std3, float* grad_x,
                 hipStream_t s);
+// ---------------------------------------------------------------------------------------------
+// Bicubic resize inside the model (resize_kernels.hip): F.interpolate(mode='bicubic', align_corners=False, antialias=False)
+// ---------------------------------------------------------------------------------------------
+// Device tables of one axis (in -> out).  idx / w [out, 4]: the clamped tap indices and cubic weights of output o.  The adjoint's
+// gather lists: input index i is named by entries adj_start[i] .. adj_start[i + 1] - 1 of (adj_o, adj_w), in (o, tap) order.
+struct ResizeAxis {
+    int in = 0, out = 0;
+    const int32_t* idx = nullptr;
+    const float* w = nullptr;
+    const int32_t* adj_start = nullptr;
+    const int32_t* adj_o = nullptr;
+    const float* adj_w = nullptr;
+};
+void resize_taps_host(int in, int out, int32_t* idx, float* w);
+// the tables of (current device, in, out): built on first use, kept for the life of the process
+int resize_axis_device(int in, int out, ResizeAxis* ax);
+// y [planes, H, W] <- x [planes, h, w]   /   gx [planes, h, w] <- gy [planes, H, W]  (gx = R_h^T gy R_w; gather, fixed order)
+int resize_bicubic_fwd(const float* x, long planes, const ResizeAxis& ah, const ResizeAxis& aw, float* y, hipStream_t s);
+int resize_bicubic_adjoint(const float* gy, long planes, const ResizeAxis& ah, const ResizeAxis& aw, float* gx, hipStream_t s);
+// im2col_normalize / col2im_grad with the resize between the [B, 3, h, w] image and the patches (delta is added before it)
+template <typename T>
+int resize_im2col_normalize(const float* x, const float* delta, int B, const ResizeAxis& ah, const ResizeAxis& aw, int P,
+                            const float* mean3, const float* std3, T* A0, long lda, int Kpad, hipStream_t s);
+template <typename T>
+int col2im_resize_grad(const T* dA0, long lda, int B, const ResizeAxis& ah, const ResizeAxis& aw, int P, const float* std3,
+                       float* grad_x, hipStream_t s);
 // tokens = [cls ; patch_out] + pos ; x0 = ln_pre(tokens)
 template <typename T>
 int embed_lnpre_fwd(const T* patch_out, long ldp, const float* cls, const float* pos,

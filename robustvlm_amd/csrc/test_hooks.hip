@@ -446,6 +446,28 @@ extern "C" int rvlm_k_col2im_grad(const void* dA0, long lda, int bf16_in, int B,
     if (bf16_in) return col2im_grad<bf16_t>((const bf16_t*)dA0, lda, B, img, P, std3, grad_x, (hipStream_t)stream);
     return col2im_grad<float>((const float*)dA0, lda, B, img, P, std3, grad_x, (hipStream_t)stream);
 }
+extern "C" int rvlm_k_resize_im2col_normalize(const float* x, const float* delta, int B, int in_h, int in_w, int img, int P,
+                                              const float* mean3, const float* std3, void* A0, long lda, int Kpad, int bf16_out,
+                                              rvlm_stream_t stream) {
+    if (!x || !A0 || !mean3 || !std3 || B <= 0 || P <= 0 || img % P != 0 || Kpad < 3 * P * P || lda < Kpad)
+        return fail(RVLM_ERR_ARG, "rvlm_k_resize_im2col_normalize: bad arguments");
+    ResizeAxis ah, aw;
+    int rc;
+    if ((rc = resize_axis_device(in_h, img, &ah)) || (rc = resize_axis_device(in_w, img, &aw))) return rc;
+    if (bf16_out)
+        return resize_im2col_normalize<bf16_t>(x, delta, B, ah, aw, P, mean3, std3, (bf16_t*)A0, lda, Kpad, (hipStream_t)stream);
+    return resize_im2col_normalize<float>(x, delta, B, ah, aw, P, mean3, std3, (float*)A0, lda, Kpad, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_col2im_resize_grad(const void* dA0, long lda, int bf16_in, int B, int in_h, int in_w, int img, int P,
+                                         const float* std3, float* grad_x, rvlm_stream_t stream) {
+    if (!dA0 || !std3 || !grad_x || B <= 0 || P <= 0 || img % P != 0 || lda < 3 * P * P)
+        return fail(RVLM_ERR_ARG, "rvlm_k_col2im_resize_grad: bad arguments");
+    ResizeAxis ah, aw;
+    int rc;
+    if ((rc = resize_axis_device(in_h, img, &ah)) || (rc = resize_axis_device(in_w, img, &aw))) return rc;
+    if (bf16_in) return col2im_resize_grad<bf16_t>((const bf16_t*)dA0, lda, B, ah, aw, P, std3, grad_x, (hipStream_t)stream);
+    return col2im_resize_grad<float>((const float*)dA0, lda, B, ah, aw, P, std3, grad_x, (hipStream_t)stream);
+}
 extern "C" int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, const float* inv_norm, float* d_raw, int B, int D,
                                        rvlm_stream_t stream) {
     return l2_normalize_bwd(d_out, e_raw, inv_norm, d_raw, B, D, (hipStream_t)stream);

@@ -1,6 +1,7 @@
 """Python handle of the native ViT forward + input-gradient engine (rvlm_vit in include/rvlm.h)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import torch
@@ -58,6 +59,7 @@ class VitEngine:
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
         self.generation = 0
         self._apgd_rho = 0.75
+        self.input_size = (cfg.image_size, cfg.image_size)
         self._h = C.c_void_p()
         c = L.VitConfigC()
         c.image_size, c.patch, c.width, c.layers = cfg.image_size, cfg.patch, cfg.width, cfg.layers
@@ -137,12 +139,40 @@ class VitEngine:
             torch.cuda.current_stream().synchronize()
         del keep
 
+    # ---- input size ----------------------------------------------------------------------------
+    def set_input_size(self, h: int = 0, w: int = 0):
+        """Images, perturbations and input gradients of every later call are ``[B, 3, h, w]``; where that is not the model's own
+        resolution the bicubic resize to it (``BicubicResize``'s operator) runs inside the patch embedding, forward and adjoint
+        (rvlm_vit_set_input_size).  ``1 <= h, w <= image_size``; ``(0, 0)`` = the model's own.  A forward saved before the change can
+        no longer be differentiated."""
+        h, w = int(h), int(w)
+        if (h, w) == (0, 0):
+            h = w = self.cfg.image_size
+        if (h, w) == self.input_size:
+            return
+        with torch.cuda.device(self.device):
+            for handle in (self._h, self._h32):
+                if handle.value:
+                    L.check(self.lib.rvlm_vit_set_input_size(handle, h, w), "rvlm_vit_set_input_size")
+        self.input_size = (h, w)
+        self.generation += 1
+
+    @contextlib.contextmanager
+    def input_size_of(self, h: int, w: int):
+        """``set_input_size(h, w)`` for the duration of a block; the previous size comes back on exit, exceptions included."""
+        before = self.input_size
+        self.set_input_size(h, w)
+        try:
+            yield self
+        finally:
+            self.set_input_size(*before)
+
     # ---- forward / backward --------------------------------------------------------------------
     def _check_images(self, x):
         _require_cuda(x, "vision")
-        c = self.cfg
-        if x.dim() != 4 or tuple(x.shape[1:]) != (3, c.image_size, c.image_size):
-            raise ValueError(f"expected [B,3,{c.image_size},{c.image_size}] images, got {tuple(x.shape)}")
+        ih, iw = self.input_size
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, ih, iw):
+            raise ValueError(f"expected [B,3,{ih},{iw}] images, got {tuple(x.shape)}")
         if x.shape[0] > self.max_batch:
             raise ValueError(f"batch {x.shape[0]} exceeds the engine's max_batch {self.max_batch}")
         if x.device != self.device:
@@ -191,8 +221,7 @@ class VitEngine:
         _require_cuda(d_emb, "d_emb")
         d = _f32c(d_emb)
         B = d.shape[0]
-        c = self.cfg
-        g = torch.empty(B, 3, c.image_size, c.image_size, device=d.device, dtype=torch.float32)
+        g = torch.empty(B, 3, *self.input_size, device=d.device, dtype=torch.float32)
         with torch.cuda.device(d.device):
             L.check(self.lib.rvlm_vit_backward_input(self._h, d.data_ptr(), B, g.data_ptr(), L.stream_ptr()),
                     "rvlm_vit_backward_input")

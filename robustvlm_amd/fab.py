@@ -67,10 +67,12 @@ class FABAttack():
         with torch.no_grad():
             return self._predict_fn(x).max(dim=1)[1]
 
-    def _engine_route(self, n, is_targeted):
+    def _engine_route(self, n, is_targeted, x=None):
+        """FAB-T on a ClassificationModel whose resizer is the identity or - for images ``x`` - one the engine runs itself
+        (a BicubicResize up to the model's resolution): df, dg come from rvlm_vit_fwd_inputgrad at the images' own size."""
         m = self.predict
         return (is_targeted and isinstance(m, ClassificationModel) and n > 1 and bool(m.logit_scale)
-                and m._identity_resizer)
+                and (m._identity_resizer or (x is not None and m.engine_input_size(x) is not None)))
 
     # ---- df, dg of one iterate on the generic route
     def get_diff_logits_grads_batch_targeted(self, imgs, la, la_target):
@@ -184,14 +186,15 @@ class FABAttack():
                 L.check(lib.rvlm_linf_random_start(im2.data_ptr(), t.data_ptr(), float(self.eps) * .5, im2[0].numel(), bs,
                                                    x1.data_ptr(), L.stream_ptr()), "rvlm_linf_random_start")
             x1.clamp_(0.0, 1.0)
-        if self._engine_route(bs, is_targeted):
+        if self._engine_route(bs, is_targeted, im2):
             # every quantity is per sample: batches beyond the engine's workspace run as chunks of >= 2 images
             mb = self.predict.model.max_batch
             bounds = list(range(0, bs, mb)) + [bs]
             if len(bounds) > 2 and bounds[-1] - bounds[-2] < 2:
                 bounds[-2] -= 1
-            parts = [self._iterate(im2[lo:hi], la2[lo:hi], la_target2[lo:hi], x1[lo:hi], True)
-                     for lo, hi in zip(bounds[:-1], bounds[1:])]
+            with self.predict.engine_route(im2):      # (a resizer the engine runs: the handle works at im2's size meanwhile)
+                parts = [self._iterate(im2[lo:hi], la2[lo:hi], la_target2[lo:hi], x1[lo:hi], True)
+                         for lo, hi in zip(bounds[:-1], bounds[1:])]
             adv, res2 = (torch.cat([p[i] for p in parts]) for i in range(2))
         else:
             adv, res2 = self._iterate(im2, la2, la_target2, x1, False)
