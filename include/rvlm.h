@@ -34,6 +34,10 @@ extern "C" {
 /* RVLM_HAS_INPUT_RESIZE: rvlm_vit_set_input_size (bicubic up-sampling as part of the model), rvlm_resize_bicubic(_adjoint),
  * rvlm_resize_taps */
 #define RVLM_HAS_INPUT_RESIZE 1
+/* RVLM_HAS_TOKENS: token-level outputs of the encoder and their input gradient - rvlm_vit_forward_tokens,
+ * rvlm_vit_backward_input_tokens, rvlm_tokens_l2_loss_grad, rvlm_vit_tokens_fwd_inputgrad, rvlm_pgd_run_tokens,
+ * RVLM_TOKENS_ALL / RVLM_TOKENS_PATCH and RVLM_FLAG_TOKENS_NONFINITE */
+#define RVLM_HAS_TOKENS 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -67,7 +71,9 @@ enum {
     RVLM_FLAG_TOKEN_RANGE = 16, /* a token id outside [0, vocab)                                  */
     RVLM_FLAG_EOT_ACTIVE = 32,  /* a prompt's EOT position (argmax of its ids) is >= active_len   */
     /* rvlm_fab_projection_linf / rvlm_fab_linf_step (RVLM_HAS_FAB) */
-    RVLM_FLAG_FAB_NONFINITE = 64 /* NaN / Inf in a row's w, t or b: that row gets lambda = 0 (no move) */
+    RVLM_FLAG_FAB_NONFINITE = 64, /* NaN / Inf in a row's w, t or b: that row gets lambda = 0 (no move) */
+    /* rvlm_tokens_l2_loss_grad and the loops built on it (RVLM_HAS_TOKENS) */
+    RVLM_FLAG_TOKENS_NONFINITE = 128 /* NaN / Inf in an image's token loss (its tokens or their reference) */
 };
 
 /* ---------------------------------------------------------------------------------------------
@@ -387,6 +393,56 @@ int rvlm_pgd_run_mixed_fwd(rvlm_vit* h, rvlm_vit* h_first, int n_first, const fl
                            const rvlm_loss_spec* loss, int norm_kind, float eps, int iterations, float stepsize, float momentum,
                            int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags, rvlm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Token-level outputs and their input gradient (RVLM_HAS_TOKENS): what a VLM reads from the tower.
+ *   LLaVA        llava/model/multimodal_encoder/clip_encoder.py:55-65, 77-90: select_layer = -2 (the last resblock dropped),
+ *                output_tokens, proj = None, feature_select takes the patch tokens [:, 1:]      -> depth = layers - 1
+ *   OpenFlamingo open_flamingo/src/factory.py:41, flamingo.py:217,242: visual.output_tokens = True, vision_encoder(x)[1]
+ *                                                                                             -> depth = layers
+ *   vlm_eval/attacks/pgd.py, apgd.py differentiate the VLM's loss through those tokens down to the pixels.
+ * depth in 1..layers = resblocks run; tokens = the fp32 residual stream after block depth - 1, all S rows [B, S, W] (class row
+ * first: the caller slices).  Plain RVLM_PREC_BF16 / F32 / F32X3 handles; a forward-provider (trainable = -2) or inference-only
+ * handle is refused where activations would be kept.  The class-token tail of the bf16 handle is bypassed for a token pass (its last
+ * block runs on every row); pooled passes before and after are unchanged.
+ * ------------------------------------------------------------------------------------------- */
+enum { RVLM_TOKENS_ALL = 0, RVLM_TOKENS_PATCH = 1 };   /* rows of the token loss: all S, or the S - 1 patch rows ([:, 1:]) */
+
+/* out_tokens [B, S, W] fp32.  ln_post = 1: ln_post applied to every row first (releases of open_clip that normalise the tokens
+ * they return); 0: the raw residual stream.  out_emb (optional, depth == layers only): the pooled embedding [B, D], un-normalised,
+ * the bits rvlm_vit_forward gives on an fp32-storage handle.  save = 1 keeps the activations for rvlm_vit_backward_input_tokens
+ * (the first ln_post pass of a handle allocates the row statistics it needs: 2 floats per token row). */
+int rvlm_vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, int B, int depth, int ln_post, int save,
+                            float* out_tokens, float* out_emb, rvlm_stream_t stream);
+
+/* grad_x [B, 3, in_h, in_w] = d(<d_tokens, tokens> + <d_emb, emb>) / dx of the token pass saved last (vlm_eval/attacks/pgd.py:
+ * torch.autograd.grad through CLIPVisionTower.forward).  d_tokens [B, S, W] fp32; d_emb [B, D] optional, depth == layers only.
+ * RVLM_ERR_STATE: no saved token pass for this B (a pooled forward, any later forward, another batch size); the pooled backwards
+ * (rvlm_vit_backward_input, _params, _input_from) return RVLM_ERR_STATE after a token forward. */
+int rvlm_vit_backward_input_tokens(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B, float* grad_x,
+                                   rvlm_stream_t stream);
+
+/* FARE's embedding loss (train/adversarial_training_clip.py:509-521) over the tokens the VLM reads, fused with the start of the
+ * backward: loss_per_sample[b] = sum over the selected rows and W of (tokens - ref_tokens)^2, ref_tokens [B, S - select, W];
+ * d = 2 (tokens - ref) (x 1 / B for RVLM_RED_MEAN) written as fp32 (seed_f32) and / or bf16 (seed_bf16), [seed_rows, W] with
+ * unselected rows and rows B S .. seed_rows - 1 zero (seed_rows = 0: B S); both NULL: loss only.  loss_scalar (optional) = mean
+ * or sum of loss_per_sample.  scratch: B * ceil(S / 8) floats.  Fixed summation order (bit-reproducible).  flags (optional)
+ * |= RVLM_FLAG_TOKENS_NONFINITE.  W % 8 == 0, 16-byte aligned pointers. */
+int rvlm_tokens_l2_loss_grad(const float* tokens, const float* ref_tokens, int B, int S, int W, int select, int reduction,
+                             float* seed_f32, uint16_t* seed_bf16, long seed_rows, float* loss_per_sample, float* loss_scalar,
+                             float* scratch, int32_t* flags, rvlm_stream_t stream);
+
+/* The token twin of rvlm_vit_fwd_inputgrad: forward to `depth` (activations kept), the token loss above against ref_tokens, input
+ * gradient.  Every output pointer is optional (out_tokens [B, S, W], out_loss_per_sample [B], out_loss_scalar [1], out_grad_x). */
+int rvlm_vit_tokens_fwd_inputgrad(rvlm_vit* h, const float* x, const float* delta, int B, int depth, int ln_post, int select,
+                                  const float* ref_tokens, int reduction, float* out_tokens, float* out_loss_per_sample,
+                                  float* out_loss_scalar, float* out_grad_x, rvlm_stream_t stream);
+
+/* rvlm_pgd_run_norm (train/pgd_train.py:5-68; vlm_eval/attacks/pgd.py) with the token loss as the model step: the unsupervised
+ * attack on what the VLM sees.  flags: RVLM_FLAG_* of the update kernels and RVLM_FLAG_TOKENS_NONFINITE. */
+int rvlm_pgd_run_tokens(rvlm_vit* h, const float* x, const float* delta0, int B, int depth, int ln_post, int select,
+                        const float* ref_tokens, int reduction, int norm_kind, float eps, int iterations, float stepsize,
+                        float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags, rvlm_stream_t stream);
+
 /* APGD L-inf.  x_init: NULL -> start from clamp(x,0,1) (apgd_train) or the caller-provided random
  * start (APGDAttack).  logits_from_head: 0 -> the `argmax(model output)==y` test runs on the
  * embedding (apgd_train quirk); 1 -> on emb @ (logit_scale*T) logits
@@ -522,7 +578,9 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * 109: rvlm_vit_backward_input_from, rvlm_vit_forward_for, rvlm_vit_set_flash_inference, rvlm_pgd_run_mixed_fwd (fp32-storage forward, bf16 backward);
                            * still 109, additions only: rvlm_text_* (CLIP text tower, forward only, announced by RVLM_HAS_TEXT);
                            * rvlm_fab_* (FAB / FAB-T L-inf), RVLM_LOSS_LOGIT_DIFF, RVLM_FLAG_FAB_NONFINITE (announced by RVLM_HAS_FAB);
-                           * rvlm_vit_set_input_size, rvlm_resize_bicubic(_adjoint), rvlm_resize_taps (announced by RVLM_HAS_INPUT_RESIZE) */
+                           * rvlm_vit_set_input_size, rvlm_resize_bicubic(_adjoint), rvlm_resize_taps (announced by RVLM_HAS_INPUT_RESIZE);
+                           * rvlm_vit_forward_tokens, rvlm_vit_backward_input_tokens, rvlm_tokens_l2_loss_grad, rvlm_vit_tokens_fwd_inputgrad,
+                           * rvlm_pgd_run_tokens, RVLM_FLAG_TOKENS_NONFINITE (announced by RVLM_HAS_TOKENS) */
 
 #ifdef __cplusplus
 }

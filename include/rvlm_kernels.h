@@ -174,6 +174,10 @@ int rvlm_k_col2im_resize_grad(const void* dA0, long lda, int bf16_in, int B, int
 int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, const float* inv_norm, float* d_raw, int B, int D,
                             rvlm_stream_t stream);
 
+/* token_kernels.hip: the start of the residual-gradient stream from a token cotangent d_tok [M, W] fp32 - d32 (fp32) and / or
+ * dlp (bf16) rows [0, M) = d_tok (+ cls_add[b, :] on row b S, cls_add [B, W] or NULL), rows [M, Mp) = 0.  W % 8 == 0. */
+int rvlm_k_tokens_seed(const float* d_tok, const float* cls_add, float* d32, uint16_t* dlp, int M, int Mp, int S, int W,
+                       rvlm_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

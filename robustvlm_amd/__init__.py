@@ -21,7 +21,7 @@ from .config import (VitConfig, CONFIGS, CLIP_MEAN, CLIP_STD, random_state_dict,
                      text_state_dict_shapes, random_text_state_dict)
 from .engine import VitEngine
 from .text_engine import TextEngine
-from .clip_model import (ClipVisionModel, ClipTextModel, ComputeLossWrapper, ClassificationModel, compute_loss, l2, ce,
+from .clip_model import (ClipVisionModel, ClipVisionTower, ClipTextModel, ComputeLossWrapper, ClassificationModel, compute_loss, l2, ce,
                          compute_acc)
 from .attack_utils import project_perturbation, normalize_grad
 from .pgd_train import pgd
@@ -40,4 +40,4 @@ __all__ = ["VitConfig", "CONFIGS", "CLIP_MEAN", "CLIP_STD", "random_state_dict",
            "l2", "ce", "compute_acc", "project_perturbation", "normalize_grad", "pgd", "apgd_train",
            "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "FABAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths",
            "TextConfig", "TEXT_CONFIGS", "text_state_dict_shapes", "random_text_state_dict", "TextEngine", "ClipTextModel",
-           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict", "BicubicResize"]
+           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict", "BicubicResize", "ClipVisionTower"]

@@ -21,6 +21,8 @@ RED_MEAN, RED_NONE = 0, 1
 FLAG_INPUT_RANGE, FLAG_NAN_GRAD, FLAG_NAN_DELTA, FLAG_ADV_RANGE = 1, 2, 4, 8
 FLAG_TOKEN_RANGE, FLAG_EOT_ACTIVE = 16, 32
 FLAG_FAB_NONFINITE = 64
+FLAG_TOKENS_NONFINITE = 128
+TOKENS_ALL, TOKENS_PATCH = 0, 1
 
 c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
 c_stream = C.c_void_p
@@ -279,6 +281,18 @@ _SIGS.update({
                                                  C.POINTER(C.c_float), C.c_void_p, C.c_long, C.c_int, C.c_int, c_stream]),
     "rvlm_k_col2im_resize_grad": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                             C.POINTER(C.c_float), c_f32p, c_stream]),
+})
+_SIGS.update({
+    # token-level outputs and their input gradient (csrc/token_kernels.hip, csrc/engine.hip; RVLM_HAS_TOKENS)
+    "rvlm_vit_forward_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_stream]),
+    "rvlm_vit_backward_input_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, c_f32p, c_stream]),
+    "rvlm_tokens_l2_loss_grad": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, C.c_long,
+                                           c_f32p, c_f32p, c_f32p, C.c_void_p, c_stream]),
+    "rvlm_vit_tokens_fwd_inputgrad": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int,
+                                                c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rvlm_pgd_run_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int,
+                                      C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, c_f32p, c_f32p, C.c_void_p, c_stream]),
+    "rvlm_k_tokens_seed": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
 })
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

@@ -7,6 +7,8 @@ Mirrors (same names, argument meaning and error behaviour):
   compute_acc          train/adversarial_training_clip.py:488-492
   ClassificationModel  CLIP_eval/clip_robustbench.py:50-69
   ClipTextModel        open_clip CLIP.encode_text as called at train/adversarial_training_clip.py:166-170
+  ClipVisionTower      llava/model/multimodal_encoder/clip_encoder.py:55-65, 77-90 (feature_select) and
+                       open_flamingo/src/factory.py:41, flamingo.py:217,242 (visual(x)[1])
 
 The arithmetic runs in librvlm.so: ``ClipVisionModel.forward`` is a torch.autograd.Function over
 rvlm_vit_forward / rvlm_vit_backward_input (so even the reference's unmodified ``pgd`` can
@@ -67,6 +69,86 @@ class ClipVisionModel(torch.nn.Module):
         return _EncodeFn.apply(vision, self.model, bool(output_normalize))
 
 
+class _TokensFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, vision, engine: VitEngine, depth: int, ln_post: bool):
+        need = ctx.needs_input_grad[0]
+        tok = engine.forward_tokens(vision, None, depth=depth, ln_post=ln_post, save=need)
+        ctx.engine = engine
+        ctx.generation = engine.generation
+        return tok
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        eng = ctx.engine
+        if eng.generation != ctx.generation:
+            raise RuntimeError("the engine's saved activations were overwritten by a later forward; "
+                               "backward must follow its forward (one graph at a time)")
+        return eng.backward_input_tokens(grad_out), None, None, None
+
+
+class ClipVisionTower(torch.nn.Module):
+    """The tower as a VLM reads it: ``forward(vision in [0,1])`` returns token features, differentiable with respect to
+    ``vision`` (rvlm_vit_forward_tokens / rvlm_vit_backward_input_tokens behind a ``torch.autograd.Function``).
+
+    ``select_layer``: -2 = the residual stream with the last resblock dropped (LLaVA: ``CLIPVisionTower.feature_select`` on
+    ``hidden_states[-2]``, clip_encoder.py:55-65, 77-90), -1 = after every block (OpenFlamingo: ``visual(x)[1]`` with
+    ``output_tokens``, factory.py:41, flamingo.py:217,242).  ``select_feature``: 'patch' drops the class row (``[:, 1:]``),
+    'cls_patch' keeps it.  ``ln_post`` normalises every token first (open_clip releases that do so for the tokens they
+    return).  ``normalize``: as for :class:`ClipVisionModel` - Normalize is fused into the engine, so the images passed here
+    are in [0,1], and an object with .mean / .std is checked against the engine's constants.
+
+    One live graph per engine: the backward reads the activations its forward left in the engine, so a second forward
+    (of this tower or any other use of the engine) before ``backward`` makes the backward raise."""
+
+    def __init__(self, model: VitEngine, select_layer: int = -2, select_feature: str = "patch", ln_post: bool = False,
+                 normalize=None):
+        super().__init__()
+        if not isinstance(model, VitEngine):
+            raise TypeError("ClipVisionTower expects a robustvlm_amd.VitEngine as `model`")
+        if select_layer not in (-1, -2):
+            raise ValueError(f"select_layer {select_layer!r}: -2 (LLaVA) or -1 (all blocks)")
+        if select_feature not in ("patch", "cls_patch"):
+            raise ValueError(f"Unexpected select feature: {select_feature}")          # clip_encoder.py:88
+        if select_layer == -2 and model.cfg.layers < 2:
+            raise ValueError("select_layer = -2 needs a tower of at least two blocks")
+        if getattr(model, "mixed", False):
+            raise ValueError(f"token passes run on the plain precisions ('bf16', 'fp32', 'x3'), not on {model.precision!r}")
+        self.model = model
+        self.select_layer = int(select_layer)
+        self.select_feature = select_feature
+        self.ln_post = bool(ln_post)
+        self.normalize = normalize
+        if normalize is not None and hasattr(normalize, "mean"):
+            m = tuple(float(v) for v in normalize.mean)
+            s = tuple(float(v) for v in normalize.std)
+            if max(abs(a - b) for a, b in zip(m + s, model.mean + model.std)) > 1e-7:
+                raise ValueError("normalize constants differ from the ones fused into the engine")
+
+    @property
+    def depth(self) -> int:
+        return self.model.cfg.layers + 1 + self.select_layer
+
+    @property
+    def hidden_size(self) -> int:
+        return self.model.cfg.width
+
+    @property
+    def num_patches(self) -> int:
+        return self.model.n_tokens - 1
+
+    def feature_select(self, tokens):
+        return tokens[:, 1:] if self.select_feature == "patch" else tokens
+
+    def forward(self, vision, output_normalize=False):
+        """``output_normalize`` exists for pgd()'s calling convention (forward(x, output_normalize=...)); tokens are never
+        L2-normalised, so anything but False is an error."""
+        if output_normalize:
+            raise ValueError("ClipVisionTower returns token features; output_normalize does not apply")
+        _require_cuda(vision, "vision")
+        return self.feature_select(_TokensFn.apply(vision, self.model, self.depth, self.ln_post))
+
+
 class ClipTextModel(torch.nn.Module):
     """``encode_text(text, normalize=False)`` with open_clip's signature over a :class:`TextEngine` - the text half of
     the frozen ``model_orig`` (train/adversarial_training_clip.py:166-170, CLIP_eval/eval_utils.py:74-78).  Forward only:
@@ -120,11 +202,39 @@ class _LossFn(torch.autograd.Function):
         return d_emb * g.reshape(-1, 1), None, None, None, None, None
 
 
+class _TokenL2Fn(torch.autograd.Function):
+    """per-image sum over rows and width of (tokens - ref)^2 and its gradient from one rvlm_tokens_l2_loss_grad call."""
+
+    @staticmethod
+    def forward(ctx, tok, ref):
+        lib = L.load()
+        t, r = _f32c(tok), _f32c(ref)
+        B, n, W = t.shape
+        per = torch.empty(B, dtype=torch.float32, device=t.device)
+        d = torch.empty_like(t)
+        scratch = torch.empty(B * ((n + 7) // 8), dtype=torch.float32, device=t.device)
+        with torch.cuda.device(t.device):
+            L.check(lib.rvlm_tokens_l2_loss_grad(t.data_ptr(), r.data_ptr(), B, n, W, L.TOKENS_ALL, L.RED_NONE, d.data_ptr(), None, 0,
+                                                 per.data_ptr(), None, scratch.data_ptr(), None, L.stream_ptr()),
+                    "rvlm_tokens_l2_loss_grad")
+        ctx.save_for_backward(d)
+        return per
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        return d * g.reshape(-1, 1, 1), None
+
+
 def l2(out, targets, reduction="none"):
-    """squared l2, not divided by the latent dimension (…clip.py:509-521)."""
+    """squared l2, not divided by the latent dimension (…clip.py:509-521).  Token features [B, n, W] (a
+    :class:`ClipVisionTower`'s output): summed over rows and width per image, on the device kernel of the token loss."""
     assert out.shape == targets.shape, f"{out.shape} != {targets.shape}"
     assert out.shape[0] > 1
     _require_cuda(out, "out")
+    if out.dim() == 3:
+        per = _TokenL2Fn.apply(out, targets)
+        return per.mean() if reduction == "mean" else per
     red = L.RED_MEAN if reduction == "mean" else L.RED_NONE
     return _LossFn.apply(out, targets, None, L.LOSS_L2, red, 1.0)
 

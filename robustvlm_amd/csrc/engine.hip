@@ -127,6 +127,13 @@ struct rvlm_vit {
     int saved_mode = 0;
     int next_param_stage = 0;   // rvlm_vit_backward_params_stages: the stage the saved forward's backward continues at
     bool saved_norm = false;
+    // token passes (rvlm_vit_forward_tokens): saved_mode 4 = the saved forward ran `saved_depth` blocks, every row of the last one
+    // (no class-token tail), and its outputs were the token rows (ln_post applied or not) - differentiated by
+    // rvlm_vit_backward_input_tokens only.  What only the ln_post form needs is allocated by the first pass that asks for it.
+    int saved_depth = 0;
+    bool saved_lnpost = false;
+    float *tok_mean = nullptr, *tok_rstd = nullptr;   // [Mp] statistics of ln_post over every token row
+    float* tok_buf = nullptr;                         // [Mp, W] ln_post(tokens) of the fused loss loop, differentiated in place
     // profiling
     bool prof = false;
     std::vector<ProfRec> recs;
@@ -502,11 +509,26 @@ static int qkv_tail_bwd(rvlm_vit* h, hipStream_t s, const void* dqkv, const Laye
     return gemm_bf16_nt(q, s);
 }
 
+// ---- token passes ---------------------------------------------------------------------------------
+// forward: run `depth` blocks (all rows), hand out the token rows; the head runs at depth == L only
+struct TokPass { int depth; int ln_post; float* out_tokens; };
+// backward: the residual-gradient stream starts from d_tokens [B, S, W] at block depth - 1 (d_tokens == null: the loss kernel
+// has written the stream already)
+struct TokSeed { const float* d_tokens; int depth; int ln_post; };
+
+static int tok_ensure(rvlm_vit* h, bool want_buf) {
+    if (!h->tok_mean) { ALLOC(h->tok_mean, (size_t)h->Mp * 4); ALLOC(h->tok_rstd, (size_t)h->Mp * 4); }
+    if (want_buf && !h->tok_buf) ALLOC(h->tok_buf, (size_t)h->Mp * h->W * 4);
+    return RVLM_OK;
+}
+
 // ---- forward -----------------------------------------------------------------------------------
 template <typename T>
 static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, int normalize, int save,
-                        float* out_emb, hipStream_t s) {
+                        float* out_emb, hipStream_t s, const TokPass* tp = nullptr) {
     const int S = h->S, W = h->W, L = h->L, D = h->D, M = B * S, M0 = B * h->G * h->G;
+    const int Lrun = tp ? tp->depth : L;            // blocks run
+    const bool tail = h->cls_tail && !tp;           // a token pass needs every row of the last block
     const double attn_flops = 4.0 * B * h->H * (double)S * S * 64;
     int rc;
     // EVERY forward overwrites state a pending backward reads (the shared LayerNorm statistics of all layers, slot 0 of
@@ -554,7 +576,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
                                          h->mean_at(0), h->rstd_at(0), B, S, W, s,
                                          save == 2 ? h->tokens : nullptr))) return rc;
     }
-    for (int l = 0; l < L; ++l) {
+    for (int l = 0; l < Lrun; ++l) {
         Layer& y = h->layers[l];
         const int sl = save ? l : 0;
         float* x_in = XS(2 * l); float* x_mid = XS(2 * l + 1); float* x_out = XS(2 * l + 2);
@@ -568,7 +590,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
             if ((rc = layernorm_fwd<T>(x_in, W, y.ln1_w, y.ln1_b, (T*)ln1o, W, h->mean_at(1 + 2 * l),
                                        h->rstd_at(1 + 2 * l), M, W, s))) return rc;
         }
-        if (h->cls_tail && l == L - 1) {
+        if (tail && l == L - 1) {
             PROF("gemm_qkv_fwd", 2.0 * M * W * 2 * W + 2.0 * B * W * W, 0);
             if ((rc = qkv_tail_fwd(h, s, ln1o, y, h->qkv[sl], B))) return rc;
         } else {
@@ -576,7 +598,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
             if ((rc = linear_fwd<T>(h, s, ln1o, W, M, 3 * W, W, y.w_in, y.w_in_nk, y.b_in, EPI_BF16,
                                     h->qkv[sl], 3 * W, nullptr, nullptr))) return rc;
         }
-        if (h->cls_tail && l == L - 1) {
+        if (tail && l == L - 1) {
             const long SW = (long)S * W;
             {
                 PROF("tail_attn_fwd", 4.0 * B * h->H * (double)S * 64, (double)M * 2 * W * sizeof(T));
@@ -628,7 +650,17 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
                                     EPI_F32_RESID, x_out, W, nullptr, x_mid))) return rc;
         }
     }
-    {
+    if (tp) {
+        PROF("tokens_out", 0, (double)M * W * 8);
+        float* xt = XS(2 * Lrun);
+        if (tp->ln_post) {
+            if ((rc = layernorm_fwd<float>(xt, W, h->lnpost_w, h->lnpost_b, tp->out_tokens ? tp->out_tokens : h->tok_buf, W, h->tok_mean,
+                                           h->tok_rstd, M, W, s))) return rc;
+        } else if (tp->out_tokens) {
+            RVLM_HIP(hipMemcpyAsync(tp->out_tokens, xt, (size_t)M * W * 4, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    if (Lrun == L) {
         PROF("head_fwd", 2.0 * B * W * D, 0);
         float* xf = XS(2 * L);
         if ((rc = layernorm_fwd<float>(xf, (long)S * W, h->lnpost_w, h->lnpost_b, h->pooled, W,
@@ -636,7 +668,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
         GemmF32 g;
         g.A = h->pooled; g.sam = W; g.sak = 1;
         g.B = h->proj; g.sbn = 1; g.sbk = D;
-        g.C = normalize ? h->emb_raw : out_emb; g.scm = D; g.scn = 1;
+        g.C = (normalize || !out_emb) ? h->emb_raw : out_emb; g.scm = D; g.scn = 1;      // (!out_emb: a token pass that did not ask for it)
         g.M = B; g.N = D; g.K = W;
         if ((rc = gemm_f32(g, s))) return rc;
         if (normalize) {
@@ -644,6 +676,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
         }
     }
     if (save) { h->saved_B = B; h->saved_norm = normalize != 0; h->saved_mode = save; h->next_param_stage = 0; }
+    if (save && tp) { h->saved_mode = 4; h->saved_depth = Lrun; h->saved_lnpost = tp->ln_post != 0; }
     if (peer) {      // (saved_mode 3: for the peer's backward only - a provider's single slots / no probabilities kept for a batched backward)
         if (h->provider || !h->own_flash) h->saved_mode = 3;
         h->exported_to = peer->uid;
@@ -667,15 +700,50 @@ widen_bf16_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, size_
 
 // ---- backward (input gradient only) --------------------------------------------------------------
 template <typename T>
-static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStream_t s, bool fp32_dres = false) {
+static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStream_t s, bool fp32_dres = false,
+                         const TokSeed* ts = nullptr) {
     const int S = h->S, W = h->W, L = h->L, D = h->D, M = B * S, M0 = B * h->G * h->G;
+    const int Ltop = ts ? ts->depth : L;            // the stream enters above block Ltop - 1
+    const bool tail = h->cls_tail && !ts;
     const double attn_flops = 8.0 * B * h->H * (double)S * S * 64;
     constexpr bool LP = !std::is_same<T, float>::value;
     // the fp32 residual-gradient stream, or none (LayerNorm backward then accumulates in the bf16 buffer, rvlm_vit::lp_dres)
     float* const dres32 = (LP && h->lp_dres && !fp32_dres) ? nullptr : h->dres;
     int rc;
     h->a3_of = nullptr;
-    {
+    if (ts) {
+        // token pass: the stream starts as the token cotangent (every row live), plus the pooled path's class rows when d_emb is given
+        PROF("tokens_seed", d_emb ? 2.0 * B * W * D : 0.0, (double)M * W * (4 + (dres32 ? 4 : 0) + (LP ? sizeof(T) : 0)));
+        const long SW = (long)S * W;
+        if (d_emb) {  // d_pooled = d_emb @ proj^T (a token pass's embedding is un-normalised)
+            GemmF32 g;
+            g.A = d_emb; g.sam = D; g.sak = 1;
+            g.B = h->proj; g.sbn = D; g.sbk = 1;
+            g.C = h->d_pooled; g.scm = W; g.scn = 1;
+            g.M = B; g.N = W; g.K = D;
+            if ((rc = gemm_f32(g, s))) return rc;
+        }
+        if (ts->d_tokens && !ts->ln_post) {
+            const float* cls_add = nullptr;
+            if (d_emb) {  // ln_post'(d_pooled) into the class rows of the fp32 buffer (a scratch where the stream is bf16 only): the seed
+                          // kernel adds them in fp32 before it rounds
+                if ((rc = layernorm_bwd<float, float>(h->d_pooled, W, h->xs[2 * L], SW, h->lnpost_w, h->mean_at(2 * L + 1),
+                                                      h->rstd_at(2 * L + 1), h->dres, SW, nullptr, SW, 0, B, W, s))) return rc;
+                cls_add = h->dres;
+            }
+            if ((rc = tokens_seed(ts->d_tokens, cls_add, SW, dres32, LP ? (bf16_t*)h->dres_lp : nullptr, M, h->Mp, S, W, s))) return rc;
+        } else if (ts->d_tokens) {
+            if (h->Mp > M) {
+                if (dres32) RVLM_HIP(hipMemsetAsync(dres32 + (size_t)M * W, 0, (size_t)(h->Mp - M) * W * 4, s));
+                if (LP) RVLM_HIP(hipMemsetAsync((T*)h->dres_lp + (size_t)M * W, 0, (size_t)(h->Mp - M) * W * sizeof(T), s));
+            }
+            if ((rc = layernorm_bwd<float, T>(ts->d_tokens, W, h->xs[2 * Ltop], W, h->lnpost_w, h->tok_mean, h->tok_rstd, dres32, W,
+                                              LP ? (T*)h->dres_lp : nullptr, W, 0, M, W, s))) return rc;
+            if (d_emb && (rc = layernorm_bwd<float, T>(h->d_pooled, W, h->xs[2 * L], SW, h->lnpost_w, h->mean_at(2 * L + 1),
+                                                       h->rstd_at(2 * L + 1), dres32, SW, LP ? (T*)h->dres_lp : nullptr, SW, 1, B, W, s)))
+                return rc;
+        }
+    } else {
         PROF("head_bwd", 2.0 * B * W * D, 0);
         const float* d_raw = d_emb;
         if (h->saved_norm) {
@@ -688,7 +756,7 @@ static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, 
         g.C = h->d_pooled; g.scm = W; g.scn = 1;
         g.M = B; g.N = W; g.K = D;
         if ((rc = gemm_f32(g, s))) return rc;
-        if (!h->cls_tail) {   // with the class-token tail the last block's ln_1 backward overwrites the other rows
+        if (!tail) {   // with the class-token tail the last block's ln_1 backward overwrites the other rows
             if (dres32) RVLM_HIP(hipMemsetAsync(dres32, 0, (size_t)h->Mp * W * 4, s));
             if (LP) RVLM_HIP(hipMemsetAsync(h->dres_lp, 0, (size_t)h->Mp * W * sizeof(T), s));
         }
@@ -697,9 +765,9 @@ static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, 
                                           LP ? (T*)h->dres_lp : nullptr, (long)S * W, 0, B, W, s))) return rc;
     }
     const void* dres_A = LP ? (const void*)h->dres_lp : (const void*)h->dres;
-    for (int l = L - 1; l >= 0; --l) {
+    for (int l = Ltop - 1; l >= 0; --l) {
         Layer& y = h->layers[l];
-        if (h->cls_tail && l == L - 1) {
+        if (tail && l == L - 1) {
             const long SW = (long)S * W;
             {
                 PROF("tail_mlp_bwd", 2.0 * B * W * 9 * W, 0);
@@ -747,7 +815,7 @@ static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, 
             if ((rc = attention_bwd<T>(h, s, h->qkv[l], h->attn_o[l], h->d_o, h->lse[l], h->dqkv, B))) return rc;
         }
         }
-        if (h->cls_tail && l == L - 1) {
+        if (tail && l == L - 1) {
             PROF("gemm_qkv_bwd", 2.0 * M * W * 2 * W + 2.0 * B * W * 3 * W, 0);
             if ((rc = qkv_tail_bwd(h, s, h->dqkv, y, h->d_ln, B))) return rc;
         } else {
@@ -759,7 +827,7 @@ static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, 
             PROF("layernorm_bwd", 0, (double)M * W * ((dres32 ? 12 : 6) + 2 * sizeof(T)));
             if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, h->xs[2 * l], W, y.ln1_w, h->mean_at(1 + 2 * l),
                                           h->rstd_at(1 + 2 * l), dres32, W, LP ? (T*)h->dres_lp : nullptr, W,
-                                          (h->cls_tail && l == L - 1) ? -S : 1, M, W, s))) return rc;
+                                          (tail && l == L - 1) ? -S : 1, M, W, s))) return rc;
         }
     }
     {
@@ -979,8 +1047,17 @@ static int vit_forward(rvlm_vit* h, const float* x, const float* delta, int B, i
     return h->bf16 ? forward_impl<bf16_t>(h, x, delta, B, normalize, save, out_emb, s)
                    : forward_impl<float>(h, x, delta, B, normalize, save, out_emb, s);
 }
+static int vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, int B, const TokPass& tp, int save, float* out_emb,
+                              hipStream_t s) {
+    return h->bf16 ? forward_impl<bf16_t>(h, x, delta, B, 0, save, out_emb, s, &tp)
+                   : forward_impl<float>(h, x, delta, B, 0, save, out_emb, s, &tp);
+}
+static int vit_backward_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int B, float* grad_x, hipStream_t s) {
+    return h->bf16 ? backward_impl<bf16_t>(h, d_emb, B, grad_x, s, false, &ts) : backward_impl<float>(h, d_emb, B, grad_x, s, false, &ts);
+}
 static int vit_backward(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStream_t s) {
     if (h->saved_mode == 3) return fail(RVLM_ERR_STATE, "backward: the saved forward was run for another handle's backward (no probabilities kept)");
+    if (h->saved_mode == 4) return fail(RVLM_ERR_STATE, "backward: the saved forward is a token pass (rvlm_vit_backward_input_tokens differentiates it)");
     return h->bf16 ? backward_impl<bf16_t>(h, d_emb, B, grad_x, s) : backward_impl<float>(h, d_emb, B, grad_x, s);
 }
 
@@ -996,6 +1073,7 @@ static int vit_backward(rvlm_vit* h, const float* d_emb, int B, float* grad_x, h
 static int vit_backward_from(rvlm_vit* hb, rvlm_vit* hx, const float* d_emb, int B, float* grad_x, hipStream_t s) {
     if (!hb->bf16 || hx->bf16) return fail(RVLM_ERR_STATE, "handoff: needs a bf16 handle and an fp32-storage (fp32 / x3) handle");
     if (hx->saved_B != B || B <= 0) return fail(RVLM_ERR_STATE, "handoff: no saved forward for this batch size on the fp32-storage handle");
+    if (hx->saved_mode == 4) return fail(RVLM_ERR_STATE, "handoff: the saved forward is a token pass (the handoff precisions take pooled passes only)");
     if (hx->lse2.empty() || hb->inference_only) return fail(RVLM_ERR_STATE, "handoff: inference-only handle");
     if (hb->Mp != hx->Mp || hb->Mp0 != hx->Mp0 || hb->W != hx->W || hb->L != hx->L || hb->S != hx->S || hb->H != hx->H ||
         hb->D != hx->D || hb->P != hx->P || hb->cfg.act != hx->cfg.act)
@@ -1390,10 +1468,15 @@ extern "C" int rvlm_vit_fwd_inputgrad(rvlm_vit* h, const float* x, const float* 
 // handle only contributes forward + loss + input gradient (what pgd_train.py:33-38 asks of the model).
 // handoff: the first iterations run forward + loss on `hf` and the input gradient on h's (bf16) kernels from hf's saved forward
 // (vit_backward_from above).
-static int pgd_run_impl(rvlm_vit* h, rvlm_vit* hf, int n_first, const float* x, const float* delta0, int B,
-                        const rvlm_loss_spec* loss, int norm_kind, float eps, int iterations, float stepsize,
-                        float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags, hipStream_t s,
-                        bool handoff = false) {
+// The model step of one iteration: forward(x + delta), loss (its scalar into lsc, when given), input gradient into grad.
+struct PooledStep {
+    rvlm_vit *h, *hf; int n_first; const rvlm_loss_spec* loss; bool handoff;
+    int operator()(int it, const float* x, const float* delta, int B, float* lsc, float* grad, hipStream_t s) const;
+};
+template <typename Step>
+static int pgd_run_impl(rvlm_vit* h, const Step& step, const float* x, const float* delta0, int B, int norm_kind, float eps,
+                        int iterations, float stepsize, float momentum, int mode_max, float* x_adv_out, float* loss_trace,
+                        int32_t* flags, hipStream_t s) {
     const size_t n = (size_t)B * 3 * h->in_h * h->in_w;
     float *delta = h->img_buf[0], *vel = h->img_buf[1], *grad = h->img_buf[2];
     int rc;
@@ -1406,14 +1489,8 @@ static int pgd_run_impl(rvlm_vit* h, rvlm_vit* hf, int n_first, const float* x, 
         RVLM_CHECK_LAUNCH();
     }
     for (int it = 0; it < iterations; ++it) {
-        rvlm_vit* m = (hf && it < n_first) ? hf : h;
-        if (handoff && m != h) m->peer = h;      // (the forward then writes h's bf16 tensors itself and keeps no probabilities)
-        rc = vit_forward(m, x, delta, B, loss->output_normalize, 1, m->emb, s);
-        m->peer = nullptr;
-        if (rc) return rc;
         float* lsc = loss_trace ? loss_trace + it : (it < 4096 ? h->loss_scalar + it : nullptr);
-        if ((rc = loss_step(m, loss, B, loss->reduction, lsc, nullptr, s))) return rc;
-        if ((rc = (handoff && m != h) ? vit_backward_from(h, m, m->d_emb, B, grad, s) : vit_backward(m, m->d_emb, B, grad, s))) return rc;
+        if ((rc = step(it, x, delta, B, lsc, grad, s))) return rc;
         {
             PROF("linf_update", 0, (double)n * 28);
             float* xo = it == iterations - 1 ? x_adv_out : nullptr;
@@ -1425,6 +1502,16 @@ static int pgd_run_impl(rvlm_vit* h, rvlm_vit* hf, int n_first, const float* x, 
     return RVLM_OK;
 }
 
+int PooledStep::operator()(int it, const float* x, const float* delta, int B, float* lsc, float* grad, hipStream_t s) const {
+    rvlm_vit* m = (hf && it < n_first) ? hf : h;
+    if (handoff && m != h) m->peer = h;      // (the forward then writes h's bf16 tensors itself and keeps no probabilities)
+    int rc = vit_forward(m, x, delta, B, loss->output_normalize, 1, m->emb, s);
+    m->peer = nullptr;
+    if (rc) return rc;
+    if ((rc = loss_step(m, loss, B, loss->reduction, lsc, nullptr, s))) return rc;
+    return (handoff && m != h) ? vit_backward_from(h, m, m->d_emb, B, grad, s) : vit_backward(m, m->d_emb, B, grad, s);
+}
+
 extern "C" int rvlm_pgd_run_norm(rvlm_vit* h, const float* x, const float* delta0, int B,
                                  const rvlm_loss_spec* loss, int norm_kind, float eps, int iterations, float stepsize,
                                  float momentum, int mode_max, float* x_adv_out, float* loss_trace,
@@ -1433,8 +1520,8 @@ extern "C" int rvlm_pgd_run_norm(rvlm_vit* h, const float* x, const float* delta
     if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_pgd_run: norm must be L-inf (0) or L2 (2)");
     RVLM_REQUIRE(B > 1 && B <= h->maxB, "rvlm_pgd_run: need 1 < B <= max_batch");
     RVLM_REQUIRE(iterations >= 0 && iterations <= 4096, "rvlm_pgd_run: iterations");
-    return pgd_run_impl(h, nullptr, 0, x, delta0, B, loss, norm_kind, eps, iterations, stepsize, momentum, mode_max,
-                        x_adv_out, loss_trace, flags, (hipStream_t)stream);
+    return pgd_run_impl(h, PooledStep{h, nullptr, 0, loss, false}, x, delta0, B, norm_kind, eps, iterations, stepsize, momentum,
+                        mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
 }
 
 // Mixed-precision loop (precision "bf16+fp32-first" of the Python mirror): the first n_first iterations on h_first - a
@@ -1456,8 +1543,8 @@ extern "C" int rvlm_pgd_run_mixed(rvlm_vit* h, rvlm_vit* h_first, int n_first, c
                  "rvlm_pgd_run_mixed: the two handles must hold the same architecture");
     RVLM_REQUIRE(!h->inference_only && !h_first->inference_only, "rvlm_pgd_run_mixed: inference-only handle");
     RVLM_REQUIRE_SAME_INPUT(h, h_first, "rvlm_pgd_run_mixed");
-    return pgd_run_impl(h, h_first, n_first, x, delta0, B, loss, norm_kind, eps, iterations, stepsize, momentum, mode_max,
-                        x_adv_out, loss_trace, flags, (hipStream_t)stream);
+    return pgd_run_impl(h, PooledStep{h, h_first, n_first, loss, false}, x, delta0, B, norm_kind, eps, iterations, stepsize, momentum,
+                        mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
 }
 
 // ... with the handoff (round 6): the first n_first iterations' FORWARD + loss on h_first (fp32 storage: x3 or fp32 precision), their
@@ -1475,8 +1562,105 @@ extern "C" int rvlm_pgd_run_mixed_fwd(rvlm_vit* h, rvlm_vit* h_first, int n_firs
     RVLM_REQUIRE(h->Mp == h_first->Mp && h->Mp0 == h_first->Mp0, "rvlm_pgd_run_mixed_fwd: the two handles need the same max_batch");
     RVLM_REQUIRE(!h->inference_only && !h_first->inference_only, "rvlm_pgd_run_mixed_fwd: inference-only handle");
     RVLM_REQUIRE_SAME_INPUT(h, h_first, "rvlm_pgd_run_mixed_fwd");
-    return pgd_run_impl(h, h_first, n_first, x, delta0, B, loss, norm_kind, eps, iterations, stepsize, momentum, mode_max,
-                        x_adv_out, loss_trace, flags, (hipStream_t)stream, true);
+    return pgd_run_impl(h, PooledStep{h, h_first, n_first, loss, true}, x, delta0, B, norm_kind, eps, iterations, stepsize, momentum,
+                        mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
+}
+
+// ---- token-level entries (RVLM_HAS_TOKENS) ---------------------------------------------------------------------------------------
+static int tokens_check(const rvlm_vit* h, int B, int depth, int save, const char* who) {
+    if (B <= 0 || B > h->maxB) return fail(RVLM_ERR_ARG, std::string(who) + ": batch exceeds max_batch");
+    if (depth < 1 || depth > h->L) return fail(RVLM_ERR_ARG, std::string(who) + ": depth must be in 1..layers");
+    if (save && h->provider) return fail(RVLM_ERR_STATE, std::string(who) + ": a forward-provider handle (trainable = -2) keeps no "
+                                                         "activations of its own: token passes run on plain bf16 / fp32 / x3 handles");
+    if (save && h->inference_only) return fail(RVLM_ERR_STATE, std::string(who) + ": inference-only handle cannot save activations");
+    return RVLM_OK;
+}
+
+extern "C" int rvlm_vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, int B, int depth, int ln_post, int save,
+                                       float* out_tokens, float* out_emb, rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && x && out_tokens, "rvlm_vit_forward_tokens: null argument");
+    int rc = tokens_check(h, B, depth, save, "rvlm_vit_forward_tokens"); if (rc) return rc;
+    RVLM_REQUIRE(!out_emb || depth == h->L, "rvlm_vit_forward_tokens: the pooled embedding exists at depth == layers only");
+    RVLM_REQUIRE(save == 0 || save == 1, "rvlm_vit_forward_tokens: save must be 0 or 1 (no weight gradients from a token pass)");
+    if (ln_post && (rc = tok_ensure(h, false))) return rc;
+    return vit_forward_tokens(h, x, delta, B, TokPass{depth, ln_post != 0, out_tokens}, save, out_emb, (hipStream_t)stream);
+}
+
+extern "C" int rvlm_vit_backward_input_tokens(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B, float* grad_x,
+                                              rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && d_tokens && grad_x, "rvlm_vit_backward_input_tokens: null argument");
+    if (h->provider || h->inference_only)
+        return fail(RVLM_ERR_STATE, "rvlm_vit_backward_input_tokens: forward-provider and inference-only handles have no backward");
+    if (B <= 0 || h->saved_B != B || h->saved_mode != 4)
+        return fail(RVLM_ERR_STATE, h->saved_B > 0 && h->saved_mode != 4
+                        ? "rvlm_vit_backward_input_tokens: the saved forward is a pooled pass (rvlm_vit_backward_input differentiates it)"
+                        : "rvlm_vit_backward_input_tokens: no saved token forward for this batch size");
+    RVLM_REQUIRE(!d_emb || h->saved_depth == h->L, "rvlm_vit_backward_input_tokens: d_emb needs a token pass of depth == layers");
+    return vit_backward_tokens(h, TokSeed{d_tokens, h->saved_depth, h->saved_lnpost}, d_emb, B, grad_x, (hipStream_t)stream);
+}
+
+// forward to `depth` + token loss (its gradient written straight into the residual-gradient stream) + input gradient
+static int tokens_step(rvlm_vit* h, const float* x, const float* delta, int B, int depth, int ln_post, int select, const float* ref,
+                       int reduction, float* out_tokens, float* lsc, int32_t* flags, float* grad, hipStream_t s) {
+    int rc;
+    if ((rc = vit_forward_tokens(h, x, delta, B, TokPass{depth, ln_post, nullptr}, 1, nullptr, s))) return rc;
+    const int S = h->S, W = h->W, M = B * S;
+    float* t = ln_post ? h->tok_buf : h->xs[2 * depth];
+    if (out_tokens) RVLM_HIP(hipMemcpyAsync(out_tokens, t, (size_t)M * W * 4, hipMemcpyDeviceToDevice, s));
+    const bool want = grad != nullptr;
+    const bool lp_only = h->bf16 && h->lp_dres;
+    {
+        PROF("tokens_loss", 3.0 * M * W, (double)M * W * (8 + (want ? (lp_only ? 2 : h->bf16 ? 6 : 4) : 0)));
+        // ln_post = 0: d goes out as the stream itself.  ln_post = 1: as fp32 over the tokens in place, for ln_post's backward.
+        float* d32 = !want ? nullptr : ln_post ? t : lp_only ? nullptr : h->dres;
+        bf16_t* dlp = (want && !ln_post && h->bf16) ? (bf16_t*)h->dres_lp : nullptr;
+        if ((rc = tokens_l2_loss_grad(t, ref, B, S, W, select, reduction, d32, dlp, ln_post ? M : h->Mp, h->loss_ps, lsc, h->loss_scratch,
+                                      flags, s))) return rc;
+    }
+    if (!want) return RVLM_OK;
+    return vit_backward_tokens(h, TokSeed{ln_post ? t : nullptr, depth, ln_post}, nullptr, B, grad, s);
+}
+static int tokens_loop_check(const rvlm_vit* h, int B, int depth, int select, const float* ref, int reduction, const char* who) {
+    int rc = tokens_check(h, B, depth, 1, who); if (rc) return rc;
+    if (!ref) return fail(RVLM_ERR_ARG, std::string(who) + ": null reference tokens");
+    if (select != RVLM_TOKENS_ALL && select != RVLM_TOKENS_PATCH) return fail(RVLM_ERR_ARG, std::string(who) + ": unknown select");
+    if (reduction != RVLM_RED_MEAN && reduction != RVLM_RED_NONE) return fail(RVLM_ERR_ARG, std::string(who) + ": unknown reduction");
+    if (tokens_l2_scratch_floats(B, h->S) > h->loss_scratch_floats) return fail(RVLM_ERR_UNSUPPORTED, std::string(who) + ": sequence too long for the loss scratch");
+    return RVLM_OK;
+}
+
+extern "C" int rvlm_vit_tokens_fwd_inputgrad(rvlm_vit* h, const float* x, const float* delta, int B, int depth, int ln_post, int select,
+                                             const float* ref_tokens, int reduction, float* out_tokens, float* out_loss_per_sample,
+                                             float* out_loss_scalar, float* out_grad_x, rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && x, "rvlm_vit_tokens_fwd_inputgrad: null argument");
+    int rc = tokens_loop_check(h, B, depth, select, ref_tokens, reduction, "rvlm_vit_tokens_fwd_inputgrad"); if (rc) return rc;
+    if (ln_post && (rc = tok_ensure(h, true))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = tokens_step(h, x, delta, B, depth, ln_post != 0, select, ref_tokens, reduction, out_tokens,
+                          out_loss_scalar ? h->loss_scalar : nullptr, nullptr, out_grad_x, s))) return rc;
+    if (out_loss_per_sample) RVLM_HIP(hipMemcpyAsync(out_loss_per_sample, h->loss_ps, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    if (out_loss_scalar) RVLM_HIP(hipMemcpyAsync(out_loss_scalar, h->loss_scalar, 4, hipMemcpyDeviceToDevice, s));
+    return RVLM_OK;
+}
+
+struct TokenStep {
+    rvlm_vit* h; int depth, ln_post, select; const float* ref; int reduction; int32_t* flags;
+    int operator()(int, const float* x, const float* delta, int B, float* lsc, float* grad, hipStream_t s) const {
+        return tokens_step(h, x, delta, B, depth, ln_post, select, ref, reduction, nullptr, lsc, flags, grad, s);
+    }
+};
+
+extern "C" int rvlm_pgd_run_tokens(rvlm_vit* h, const float* x, const float* delta0, int B, int depth, int ln_post, int select,
+                                   const float* ref_tokens, int reduction, int norm_kind, float eps, int iterations, float stepsize,
+                                   float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags,
+                                   rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && x && x_adv_out, "rvlm_pgd_run_tokens: null argument");
+    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_pgd_run_tokens: norm must be L-inf (0) or L2 (2)");
+    RVLM_REQUIRE(iterations >= 0 && iterations <= 4096, "rvlm_pgd_run_tokens: iterations");
+    int rc = tokens_loop_check(h, B, depth, select, ref_tokens, reduction, "rvlm_pgd_run_tokens"); if (rc) return rc;
+    if (ln_post && (rc = tok_ensure(h, true))) return rc;
+    return pgd_run_impl(h, TokenStep{h, depth, ln_post != 0, select, ref_tokens, reduction, flags}, x, delta0, B, norm_kind, eps,
+                        iterations, stepsize, momentum, mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
 }
 
 extern "C" int rvlm_pgd_run(rvlm_vit* h, const float* x, const float* delta0, int B,

@@ -240,4 +240,16 @@ int pos_cls_grad(const float* dtok, long ld, int B, int S, int W, float* dpos, f
 template <typename T>
 int gather_patch_rows(const float* dtok, long ld, int B, int S, int W, T* d_patch, long ldp, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// token-level cotangents (token_kernels.hip)
+// ---------------------------------------------------------------------------------------------
+// the start of the residual-gradient stream from a [M, W] fp32 cotangent: d32 and / or dlp (whichever the backward runs on) rows
+// [0, M) = d_tok (+ cls_add[b] on row b S; cls_add may be the class rows of d32 itself, ld_cls = S W), rows [M, Mp) = 0
+int tokens_seed(const float* d_tok, const float* cls_add, long ld_cls, float* d32, bf16_t* dlp, int M, int Mp, int S, int W,
+                hipStream_t s);
+// rvlm_tokens_l2_loss_grad (include/rvlm.h) with the bf16 seed typed; scratch: tokens_l2_scratch_floats(B, S) floats
+size_t tokens_l2_scratch_floats(int B, int S);
+int tokens_l2_loss_grad(const float* t, const float* ref, int B, int S, int W, int select, int reduction, float* d32, bf16_t* dlp,
+                        long seed_rows, float* per_sample, float* scalar, float* scratch, int32_t* flags, hipStream_t s);
+
 }  // namespace rvlm

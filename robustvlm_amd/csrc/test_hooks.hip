@@ -472,3 +472,7 @@ extern "C" int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, c
                                        rvlm_stream_t stream) {
     return l2_normalize_bwd(d_out, e_raw, inv_norm, d_raw, B, D, (hipStream_t)stream);
 }
+extern "C" int rvlm_k_tokens_seed(const float* d_tok, const float* cls_add, float* d32, uint16_t* dlp, int M, int Mp, int S, int W,
+                                  rvlm_stream_t stream) {
+    return tokens_seed(d_tok, cls_add, W, d32, (bf16_t*)dlp, M, Mp, S, W, (hipStream_t)stream);
+}

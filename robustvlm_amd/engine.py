@@ -275,6 +275,121 @@ class VitEngine:
         self.generation += 1
         return emb, per, scalar.reshape(()), g
 
+    # ---- token-level passes (what a VLM reads from the tower) ------------------------------------------
+    @property
+    def n_tokens(self) -> int:
+        return (self.cfg.image_size // self.cfg.patch) ** 2 + 1
+
+    def _token_handle(self, what: str):
+        if self.mixed:
+            raise ValueError(f"{what}: token passes run on the plain precisions ('bf16', 'fp32', 'x3'), not on {self.precision!r}")
+        return self._h
+
+    def _depth(self, depth) -> int:
+        L_ = self.cfg.layers
+        d = L_ if depth is None else int(depth)
+        if d <= 0:                      # LLaVA's select_layer convention: -1 = after the last block, -2 = one block earlier
+            d = L_ + 1 + d
+        if not 1 <= d <= L_:
+            raise ValueError(f"depth {depth!r} outside 1..{L_} (or -{L_}..-1)")
+        return d
+
+    def forward_tokens(self, x, delta=None, depth=None, ln_post=False, save=False, return_emb=False):
+        """The residual stream after ``depth`` resblocks, ``[B, S, W]`` with the class row first (rvlm_vit_forward_tokens):
+        ``depth = layers - 1`` (or -2) is LLaVA's tower, ``layers`` (None, -1) what open_clip returns with ``output_tokens``.
+        ``ln_post`` normalises every row first.  ``return_emb`` (full depth only) also returns the pooled embedding."""
+        h = self._token_handle("forward_tokens")
+        self._check_images(x)
+        x = _f32c(x)
+        d = _f32c(delta) if delta is not None else None
+        depth = self._depth(depth)
+        if return_emb and depth != self.cfg.layers:
+            raise ValueError("the pooled embedding exists at full depth only")
+        B = x.shape[0]
+        tok = torch.empty(B, self.n_tokens, self.cfg.width, device=x.device, dtype=torch.float32)
+        emb = torch.empty(B, self.cfg.out_dim, device=x.device, dtype=torch.float32) if return_emb else None
+        with torch.cuda.device(x.device):
+            L.check(self.lib.rvlm_vit_forward_tokens(h, x.data_ptr(), L.ptr(d), B, depth, int(bool(ln_post)), int(bool(save)),
+                                                     tok.data_ptr(), L.ptr(emb), L.stream_ptr()), "rvlm_vit_forward_tokens")
+        self.generation += 1
+        return (tok, emb) if return_emb else tok
+
+    def backward_input_tokens(self, d_tokens, d_emb=None) -> torch.Tensor:
+        """Input gradient of ``<d_tokens, tokens> (+ <d_emb, emb>)`` of the last ``forward_tokens(..., save=True)``."""
+        h = self._token_handle("backward_input_tokens")
+        _require_cuda(d_tokens, "d_tokens")
+        dt = _f32c(d_tokens)
+        if dt.dim() != 3 or tuple(dt.shape[1:]) != (self.n_tokens, self.cfg.width):
+            raise ValueError(f"expected a [B,{self.n_tokens},{self.cfg.width}] cotangent, got {tuple(dt.shape)}")
+        B = dt.shape[0]
+        de = None
+        if d_emb is not None:
+            _require_cuda(d_emb, "d_emb")
+            de = _f32c(d_emb)
+            if tuple(de.shape) != (B, self.cfg.out_dim):
+                raise ValueError(f"expected a [{B},{self.cfg.out_dim}] embedding cotangent, got {tuple(de.shape)}")
+        g = torch.empty(B, 3, *self.input_size, device=dt.device, dtype=torch.float32)
+        with torch.cuda.device(dt.device):
+            L.check(self.lib.rvlm_vit_backward_input_tokens(h, dt.data_ptr(), L.ptr(de), B, g.data_ptr(), L.stream_ptr()),
+                    "rvlm_vit_backward_input_tokens")
+        return g
+
+    def _token_ref(self, ref, B, select):
+        _require_cuda(ref, "ref_tokens")
+        if select not in ("all", "patch"):
+            raise ValueError(f"select {select!r}: 'all' or 'patch'")
+        n = self.n_tokens - (1 if select == "patch" else 0)
+        ref = _f32c(ref)
+        if tuple(ref.shape) != (B, n, self.cfg.width):
+            raise ValueError(f"select={select!r} needs reference tokens [{B},{n},{self.cfg.width}], got {tuple(ref.shape)}")
+        if ref.device != self.device:
+            raise ValueError(f"ref_tokens live on {ref.device}, the engine on {self.device}")
+        return ref, (L.TOKENS_PATCH if select == "patch" else L.TOKENS_ALL)
+
+    def tokens_fwd_inputgrad(self, x, delta, ref_tokens, depth=None, ln_post=False, select="all", reduction="mean",
+                             want_tokens=False):
+        """One iteration of the token-FARE attack in one native call (rvlm_vit_tokens_fwd_inputgrad): forward to ``depth``,
+        ``sum (tokens - ref)^2`` per image over all rows or the patch rows, input gradient of its mean (or sum).
+        Returns (tokens | None, loss_per_sample, loss_scalar, grad_x)."""
+        h = self._token_handle("tokens_fwd_inputgrad")
+        self._check_images(x)
+        x = _f32c(x)
+        d = _f32c(delta) if delta is not None else None
+        B = x.shape[0]
+        ref, sel = self._token_ref(ref_tokens, B, select)
+        red = {"mean": L.RED_MEAN, "none": L.RED_NONE}[reduction]
+        tok = torch.empty(B, self.n_tokens, self.cfg.width, device=x.device, dtype=torch.float32) if want_tokens else None
+        per = torch.empty(B, device=x.device, dtype=torch.float32)
+        scalar = torch.empty(1, device=x.device, dtype=torch.float32)
+        g = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.check(self.lib.rvlm_vit_tokens_fwd_inputgrad(h, x.data_ptr(), L.ptr(d), B, self._depth(depth), int(bool(ln_post)), sel,
+                                                           ref.data_ptr(), red, L.ptr(tok), per.data_ptr(), scalar.data_ptr(),
+                                                           g.data_ptr(), L.stream_ptr()), "rvlm_vit_tokens_fwd_inputgrad")
+        self.generation += 1
+        return tok, per, scalar.reshape(()), g
+
+    def pgd_run_tokens(self, x, delta0, ref_tokens, eps, iterations, stepsize, momentum, mode, depth=None, ln_post=False,
+                       select="all", reduction="mean", want_trace=False, norm_kind=0):
+        """Whole pgd() loop on the device with the token loss as the model step (rvlm_pgd_run_tokens).
+        Returns (x_adv, flags, loss_trace | None)."""
+        h = self._token_handle("pgd_run_tokens")
+        self._check_images(x)
+        x = _f32c(x)
+        d0 = _f32c(delta0) if delta0 is not None else None
+        ref, sel = self._token_ref(ref_tokens, x.shape[0], select)
+        red = {"mean": L.RED_MEAN, "none": L.RED_NONE}[reduction]
+        out = torch.empty_like(x)
+        flags = torch.zeros(1, dtype=torch.int32, device=x.device)
+        trace = torch.zeros(max(iterations, 1), dtype=torch.float32, device=x.device) if want_trace else None
+        with torch.cuda.device(x.device):
+            L.check(self.lib.rvlm_pgd_run_tokens(h, x.data_ptr(), L.ptr(d0), x.shape[0], self._depth(depth), int(bool(ln_post)), sel,
+                                                 ref.data_ptr(), red, int(norm_kind), float(eps), int(iterations), float(stepsize),
+                                                 float(momentum), 1 if mode == "max" else 0, out.data_ptr(), L.ptr(trace),
+                                                 flags.data_ptr(), L.stream_ptr()), "rvlm_pgd_run_tokens")
+        self.generation += 1
+        return out, flags, trace
+
     # ---- fused loops -----------------------------------------------------------------------------
     def _loss_spec(self, loss_kind, reduction, output_normalize, ref, targets, logit_scale, y_target=None, B=None):
         """The C loops take raw device pointers: everything the reference would catch with an assert / a shape error /

@@ -7,6 +7,8 @@ Same signature, same semantics, same exceptions.  Two execution routes, both on 
   (encoder forward, loss, input-gradient backward, Linf update) is ONE call into librvlm.so
   (rvlm_pgd_run) with no host synchronisation; the reference's per-iteration asserts
   (:24, :40-42, :60-63) are accumulated in a device flag word and raised once after the loop.
+* fused tokens - ``forward`` is a :class:`ClipVisionTower` (the tower as LLaVA / OpenFlamingo read it) and ``loss_fn`` the
+  l2 ``ComputeLossWrapper`` on a ``[B, n, W]`` token reference: the same loop with the token loss (rvlm_pgd_run_tokens).
 * generic - any differentiable ``forward`` / ``loss_fn``: torch autograd supplies the gradient, the
   fused HIP kernel rvlm_pgd_linf_update does sign/momentum/step/project/clamp in one pass.
 """
@@ -16,7 +18,7 @@ import torch
 
 from . import _lib as L
 from .attack_utils import LINF, L2, normalize_grad, project_perturbation
-from .clip_model import ClipVisionModel, ComputeLossWrapper
+from .clip_model import ClipVisionModel, ClipVisionTower, ComputeLossWrapper
 from .engine import _require_cuda, _f32c
 
 
@@ -47,6 +49,19 @@ def pgd(forward, loss_fn, data_clean, targets, norm, eps, iterations, stepsize, 
             data_clean, perturbation, kind, loss_fn.reduction, ref, targets, output_normalize, eps,
             iterations, stepsize, momentum, mode, loss_fn.logit_scale, norm_kind=0 if norm in LINF else 2)
         _raise_from_flags(int(flags.item()))          # the loop's only host sync
+        return x_adv
+
+    # ---- fused token route: a ClipVisionTower and FARE's l2 over the tokens it returns (rvlm_pgd_run_tokens) -------------------
+    if (isinstance(forward, ClipVisionTower) and isinstance(loss_fn, ComputeLossWrapper) and not verbose
+            and loss_fn.loss_str == "l2" and loss_fn.reduction in ("mean", "none") and data_clean.shape[0] > 1
+            and not output_normalize and isinstance(loss_fn.embedding_orig, torch.Tensor) and loss_fn.embedding_orig.dim() == 3):
+        x_adv, flags, _ = forward.model.pgd_run_tokens(
+            data_clean, perturbation, loss_fn.embedding_orig, eps, iterations, stepsize, momentum, mode, depth=forward.depth,
+            ln_post=forward.ln_post, select="patch" if forward.select_feature == "patch" else "all", reduction=loss_fn.reduction,
+            norm_kind=0 if norm in LINF else 2)
+        flags = int(flags.item())                     # the loop's only host sync
+        assert not (flags & L.FLAG_TOKENS_NONFINITE), "non-finite token loss"
+        _raise_from_flags(flags)
         return x_adv
 
     # ---- generic route: autograd for the model, fused HIP kernel for the update -----------------
