@@ -21,6 +21,16 @@ struct Layer {
     bf16_t *w_in_nk, *w_in_t, *w_out_nk, *w_out_t, *w_fc_nk, *w_fc_t, *w_proj_nk, *w_proj_t;  // bf16
 };
 
+// What kind of forward a handle holds saved (meaningful while saved_B > 0).  Input and Params are the values of the C ABI's
+// save_for_backward (1, 2); the other two are set by the forward itself.
+enum class Saved {
+    None = 0,
+    Input = 1,      // activations of the input-gradient chain
+    Params = 2,     // ... and the inputs of every linear layer (trainable handles)
+    ForPeer = 3,    // run for another handle's backward (FwdPass::peer): a provider's single slots / no probabilities kept
+    Tokens = 4,     // a token pass: saved_depth blocks, every row of the last one, token rows as outputs
+};
+
 struct ProfRec { int cls; hipEvent_t a, b; };
 struct ProfAcc { double ms = 0, flops = 0, bytes = 0; int64_t n = 0; };
 
@@ -50,18 +60,11 @@ struct rvlm_vit {
     std::vector<float*> lse;     // L x [B*H*Sp]
     std::vector<float*> lse2;    // fp32 storage: L x [B*H*Sp], the flash kernels' log-sum-exp rows, written by the softmax pass of a
                                  // saving forward for the handoff to a bf16 handle's backward (vit_backward_from)
-    float* cur_lse2 = nullptr;   // ... of the block the forward is in
-    // Forward FOR a bf16 handle (the handoff, vit_backward_from): `peer` is set for the duration of a saving forward whose input
-    // gradient that handle will evaluate.  The attention then runs as the fp32 flash kernel (no probabilities kept: this handle's
-    // own backward is refused for that pass, saved_mode 3), which writes the peer's bf16 qkv / attention output / log-sum-exp rows as
-    // it goes; the split-bf16 activation pass writes the peer's act'(fc1).  What was exported is remembered per saved forward.
-    rvlm_vit* peer = nullptr;
+    // A saving forward run FOR a bf16 handle (the handoff, FwdPass::peer) writes that handle's bf16 qkv / attention output / act'(fc1)
+    // as it goes.  What was exported is remembered per saved forward.
     unsigned long long uid = 0;          // unique per created handle (never reused, unlike an address)
     unsigned long long exported_to = 0;  // uid of the handle the saved forward's bf16 qkv / attention output / lse rows already sit in
     bool exported_dact = false;          // ... and its act'(fc1)
-    bf16_t* cur_dact_out = nullptr;      // the peer's act'(fc1) buffer of the block the forward is in
-    bf16_t *cur_qkv_bf = nullptr, *cur_o_bf = nullptr;
-    bool cur_flash = false;              // this forward's attention runs as the flash kernel
     // Non-saving forwards on the flash kernel too (rvlm_vit_set_flash_inference).  OFF by default: a handle's saving and non-saving
     // forwards must agree BIT FOR BIT - FARE's loss at delta = 0 is |phi(x) - phi(x)|^2 = 0 with a zero gradient exactly (apgd_train
     // starts there, train/apgd_train.py:157-160), and 1e-7 of rounding difference between two attention paths turns that into a
@@ -124,10 +127,10 @@ struct rvlm_vit {
     std::vector<void*> allocs;
     size_t bytes = 0;
     int saved_B = 0;
-    int saved_mode = 0;
+    Saved saved_mode = Saved::None;
     int next_param_stage = 0;   // rvlm_vit_backward_params_stages: the stage the saved forward's backward continues at
     bool saved_norm = false;
-    // token passes (rvlm_vit_forward_tokens): saved_mode 4 = the saved forward ran `saved_depth` blocks, every row of the last one
+    // token passes (rvlm_vit_forward_tokens): Saved::Tokens = the saved forward ran `saved_depth` blocks, every row of the last one
     // (no class-token tail), and its outputs were the token rows (ln_post applied or not) - differentiated by
     // rvlm_vit_backward_input_tokens only.  What only the ln_post form needs is allocated by the first pass that asks for it.
     int saved_depth = 0;
@@ -171,8 +174,8 @@ static int prof_class(rvlm_vit* h, const char* name) {
 }
 struct ProfScope {
     rvlm_vit* h; hipStream_t s; int idx = -1;
-    ProfScope(rvlm_vit* h_, hipStream_t s_, const char* name, double flops, double bytes) : h(h_), s(s_) {
-        if (!h->prof) return;
+    ProfScope(rvlm_vit* h_, hipStream_t s_, const char* name, double flops, double bytes) : h(h_), s(s_) {   // (null name: no scope)
+        if (!h->prof || !name) return;
         ProfRec r;
         r.cls = prof_class(h, name);
         (void)hipEventCreate(&r.a); (void)hipEventCreate(&r.b);
@@ -186,6 +189,8 @@ struct ProfScope {
     ~ProfScope() { if (idx >= 0) (void)hipEventRecord(h->recs[idx].b, s); }
 };
 #define PROF(name, flops, bytes) ProfScope _ps(h, s, name, (double)(flops), (double)(bytes))
+// ... recorded only where `on` holds (the walkers: a pass that records no scopes; a step the class-token tail accounts coarsely)
+#define PROF_IF(on, name, flops, bytes) ProfScope _ps(h, s, (on) ? name : nullptr, (double)(flops), (double)(bytes))
 
 // ---- weights --------------------------------------------------------------------------------
 static int copy_f32(rvlm_vit* h, float** dst, const float* src, size_t n, hipStream_t s, bool alloc) {
@@ -265,7 +270,8 @@ static inline void with_scratch(const rvlm_vit* h, GemmBf16& g) { g.splitk = h->
 template <typename T>
 static int linear_fwd(rvlm_vit* h, hipStream_t s, const void* A, long lda, int M, int N, int K,
                       const float* w_f32, const bf16_t* w_nk, const float* bias, int epi, void* out, long ldo,
-                      void* out_pre, const float* residual, int a_rows = 0);
+                      void* out_pre, const float* residual, int a_rows = 0, bf16_t* dact_out = nullptr);
+// (dact_out, fp32 storage with EPI_BF16_ACT: act'(fc1) in bf16 for the bf16 handle this forward runs for, FwdPass::peer)
 // x3 mode: the encoder linears whose shapes the persistent bf16 GEMM takes (everything else - the patch embedding with its
 // K = 3 P^2, tiny test models - stays on the fp32 tiles)
 static inline bool x3_takes(const rvlm_vit* h, int M, int N, int K) {
@@ -274,7 +280,7 @@ static inline bool x3_takes(const rvlm_vit* h, int M, int N, int K) {
 template <>
 int linear_fwd<bf16_t>(rvlm_vit* h, hipStream_t s, const void* A, long lda, int M, int N, int K,
                        const float*, const bf16_t* w_nk, const float* bias, int epi, void* out, long ldo,
-                       void* out_pre, const float* residual, int a_rows) {
+                       void* out_pre, const float* residual, int a_rows, bf16_t*) {
     GemmBf16 g;
     g.A = (const bf16_t*)A; g.lda = lda; g.Bw = w_nk; g.ldb = K; g.M = M; g.N = N; g.K = K;
     g.a_rows = a_rows > 0 ? a_rows : (int)round_up(M, 128); g.epi = epi; g.bias = bias; g.out = out; g.ldo = ldo;
@@ -285,7 +291,7 @@ int linear_fwd<bf16_t>(rvlm_vit* h, hipStream_t s, const void* A, long lda, int 
 template <>
 int linear_fwd<float>(rvlm_vit* h, hipStream_t s, const void* A, long lda, int M, int N, int K,
                       const float* w_f32, const bf16_t* w_nk, const float* bias, int epi, void* out, long ldo,
-                      void* out_pre, const float* residual, int) {
+                      void* out_pre, const float* residual, int, bf16_t* dact_out) {
     if (x3_takes(h, M, N, K) && w_nk) {
         // split-bf16: A3 = [A_hi | A_hi | A_lo] against W3 = [W_hi | W_lo | W_hi] - one bf16 GEMM of contraction length 3 K with an
         // fp32 epilogue; the activation (fc1) runs as its own pass over the fp32 pre-activation
@@ -305,9 +311,9 @@ int linear_fwd<float>(rvlm_vit* h, hipStream_t s, const void* A, long lda, int M
             // (its only other reader is the weight gradient, which this precision does not have)
             const bool fuse = x3_takes(h, M, K, N);      // fc2's own rule: [M, N] x [K, N]^T
             if ((rc = x3_act((const float*)g.out, ldo, (float*)out, ldo, fuse ? h->a3 : nullptr, M, (int)round_up(M, 256), N, h->cfg.act, 0, s,
-                             h->cur_dact_out, ldo)))
+                             dact_out, ldo)))
                 return rc;
-            if (h->cur_dact_out) h->exported_dact = true;
+            if (dact_out) h->exported_dact = true;
             if (fuse) h->a3_of = out;
         }
         return RVLM_OK;
@@ -319,8 +325,8 @@ int linear_fwd<float>(rvlm_vit* h, hipStream_t s, const void* A, long lda, int M
     g.M = M; g.N = N; g.K = K; g.bias = bias; g.residual = residual;
     if (epi == EPI_BF16_ACT) { g.act = h->cfg.act; g.C_pre = (float*)out_pre; }
     int rc = gemm_f32(g, s);
-    if (rc == RVLM_OK && epi == EPI_BF16_ACT && h->cur_dact_out && out_pre) {      // a forward for a peer on the fp32 tiles: act'(h) for it
-        rc = x3_export_bf16((const float*)out_pre, ldo, h->cur_dact_out, ldo, M, N, h->cfg.act, 1, s);
+    if (rc == RVLM_OK && epi == EPI_BF16_ACT && dact_out && out_pre) {      // a forward for a peer on the fp32 tiles: act'(h) for it
+        rc = x3_export_bf16((const float*)out_pre, ldo, dact_out, ldo, M, N, h->cfg.act, 1, s);
         h->exported_dact = true;
     }
     return rc;
@@ -383,10 +389,16 @@ static bool ln_into_split(rvlm_vit* h, hipStream_t s, const float* x, const floa
 }
 
 // ---- attention (dispatch on precision) -------------------------------------------------------
+// What a forward pass decides once, at its top (forward_impl): the bf16 handle it runs for (the handoff) or none, and whether its
+// attention runs as the fp32 flash kernel.
+struct FwdPass { rvlm_vit* peer = nullptr; bool flash = false; };
+// (fp32 storage only: lse2 = the block's log-sum-exp rows or null; qkv_bf / o_bf = the peer's bf16 qkv / attention output or null)
 template <typename T>
-static int attention_fwd(rvlm_vit* h, hipStream_t s, const void* qkv, void* o, float* lse, int B);
+static int attention_fwd(rvlm_vit* h, hipStream_t s, const FwdPass& fp, const void* qkv, void* o, float* lse, float* lse2,
+                         bf16_t* qkv_bf, bf16_t* o_bf, int B);
 template <>
-int attention_fwd<bf16_t>(rvlm_vit* h, hipStream_t s, const void* qkv, void* o, float* lse, int B) {
+int attention_fwd<bf16_t>(rvlm_vit* h, hipStream_t s, const FwdPass&, const void* qkv, void* o, float* lse, float*, bf16_t*, bf16_t*,
+                          int B) {
     return attn_fwd_bf16((const bf16_t*)qkv, 3 * h->W, (bf16_t*)o, h->W, lse, B, h->H, h->S, s);
 }
 // fp32 mode: the score matrices are materialised as [B, H, S, Sld] with Sld = round_up(S, 4) and zero pad columns (never
@@ -395,7 +407,7 @@ int attention_fwd<bf16_t>(rvlm_vit* h, hipStream_t s, const void* qkv, void* o, 
 // P = softmax(0.125 Q K^T) of one block into `P` ([B, H, S, Sld]): the block's slot of rvlm_vit::lse, which in fp32 mode holds
 // the probabilities themselves - the backward reads them back instead of recomputing scores + softmax (round 5: 13 GB for
 // ViT-L/14 at B = 128 of 288, one batched GEMM + one softmax pass less per block and backward)
-static int attn_scores_f32(rvlm_vit* h, hipStream_t s, const float* qkv, float* P, int B) {
+static int attn_scores_f32(rvlm_vit* h, hipStream_t s, const float* qkv, float* P, float* lse2, int B) {
     const int S = h->S, W = h->W, H = h->H, Sld = (int)round_up(S, 4);
     GemmF32 g;  // scores = 0.125 * Q K^T
     g.A = qkv; g.sam = 3 * W; g.sak = 1; g.sab1 = (long)S * 3 * W; g.sab2 = 64;
@@ -403,19 +415,20 @@ static int attn_scores_f32(rvlm_vit* h, hipStream_t s, const float* qkv, float* 
     g.C = P; g.scm = Sld; g.scn = 1; g.scb1 = (long)H * S * Sld; g.scb2 = (long)S * Sld;
     g.M = S; g.N = S; g.K = 64; g.nb1 = B; g.nb2 = H; g.alpha = 0.125f;
     int rc = gemm_f32(g, s); if (rc) return rc;
-    return softmax_rows_fwd(P, (long)B * H * S, S, Sld, s, h->cur_lse2, (int)round_up(S, 32));
+    return softmax_rows_fwd(P, (long)B * H * S, S, Sld, s, lse2, (int)round_up(S, 32));
 }
 template <>
-int attention_fwd<float>(rvlm_vit* h, hipStream_t s, const void* qkv_, void* o, float* P, int B) {
+int attention_fwd<float>(rvlm_vit* h, hipStream_t s, const FwdPass& fp, const void* qkv_, void* o, float* P, float* lse2,
+                         bf16_t* qkv_bf, bf16_t* o_bf, int B) {
     const int S = h->S, W = h->W, H = h->H, Sld = (int)round_up(S, 4);
     const float* qkv = (const float*)qkv_;
     int rc = RVLM_OK;
-    if (h->cur_flash) {      // no backward of this handle's own will read P: one fused kernel, no score matrices
-        if (attn_fwd_f32_flash(qkv, (float*)o, h->cur_lse2, (int)round_up(S, 32), h->cur_qkv_bf, h->cur_o_bf, B, H, S, s, &rc)) return rc;
-        if (h->peer || h->own_flash)      // (no fall-through: there is no probability buffer behind P on these paths)
+    if (fp.flash) {      // no backward of this handle's own will read P: one fused kernel, no score matrices
+        if (attn_fwd_f32_flash(qkv, (float*)o, lse2, (int)round_up(S, 32), qkv_bf, o_bf, B, H, S, s, &rc)) return rc;
+        if (fp.peer || h->own_flash)      // (no fall-through: there is no probability buffer behind P on these paths)
             return fail(RVLM_ERR_UNSUPPORTED, "attention forward: sequence length not covered by the fp32 flash kernel");
     }
-    rc = attn_scores_f32(h, s, qkv, P, B); if (rc) return rc;
+    rc = attn_scores_f32(h, s, qkv, P, lse2, B); if (rc) return rc;
     GemmF32 g;  // O = P V
     g.A = P; g.sam = Sld; g.sak = 1; g.sab1 = (long)H * S * Sld; g.sab2 = (long)S * Sld; g.pad4 = 1;
     g.B = qkv + 2 * W; g.sbn = 1; g.sbk = 3 * W; g.sbb1 = (long)S * 3 * W; g.sbb2 = 64;
@@ -423,25 +436,26 @@ int attention_fwd<float>(rvlm_vit* h, hipStream_t s, const void* qkv_, void* o, 
     g.M = S; g.N = 64; g.K = S; g.nb1 = B; g.nb2 = H;
     return gemm_f32(g, s);
 }
+// (lse: the saved forward's log-sum-exp rows - bf16 - or probabilities - fp32 batched path; lse2: the fp32 flash kernels' rows or null)
 template <typename T>
 static int attention_bwd(rvlm_vit* h, hipStream_t s, const void* qkv, const void* o, const void* d_o,
-                         const float* lse, void* dqkv, int B);
+                         const float* lse, const float* lse2, void* dqkv, int B);
 template <>
 int attention_bwd<bf16_t>(rvlm_vit* h, hipStream_t s, const void* qkv, const void* o, const void* d_o,
-                          const float* lse, void* dqkv, int B) {
+                          const float* lse, const float*, void* dqkv, int B) {
     return attn_bwd_bf16((const bf16_t*)qkv, 3 * h->W, (const bf16_t*)o, h->W, (const bf16_t*)d_o, h->W,
                          lse, h->dsum, (bf16_t*)dqkv, 3 * h->W, B, h->H, h->S, s);
 }
 template <>
 int attention_bwd<float>(rvlm_vit* h, hipStream_t s, const void* qkv_, const void* o_, const void* d_o_,
-                         const float* P, void* dqkv_, int B) {
+                         const float* P, const float* lse2, void* dqkv_, int B) {
     const int S = h->S, W = h->W, H = h->H, Sld = (int)round_up(S, 4);
     const float* qkv = (const float*)qkv_;
     const float* d_o = (const float*)d_o_;
     float* dqkv = (float*)dqkv_;
     int rc = RVLM_OK;                                             // (P: kept by the forward)
-    if (h->own_flash) {      // probabilities recomputed from the forward's log-sum-exp rows (cur_lse2: the block's)
-        if (attn_bwd_f32_flash(qkv, (const float*)o_, d_o, h->cur_lse2, (int)round_up(S, 32), h->dsum, dqkv, B, H, S, s, &rc)) return rc;
+    if (h->own_flash) {      // probabilities recomputed from the forward's log-sum-exp rows
+        if (attn_bwd_f32_flash(qkv, (const float*)o_, d_o, lse2, (int)round_up(S, 32), h->dsum, dqkv, B, H, S, s, &rc)) return rc;
         return fail(RVLM_ERR_STATE, "attention backward: flash kernels refused a sequence length they cover");
     }
     const long bs1 = (long)H * S * Sld, bs2 = (long)S * Sld, qs1 = (long)S * 3 * W, os1 = (long)S * W;
@@ -522,10 +536,18 @@ static int tok_ensure(rvlm_vit* h, bool want_buf) {
     return RVLM_OK;
 }
 
+// ---- row geometry of a transformer block ---------------------------------------------------------
+// Which rows of a block are live downstream of its attention, as the (M, leading dimension) the steps after the attention run on.
+// Every row: {B*S, W, 0}.  Class-token tail (rvlm_vit::cls_tail, last block of a pooled bf16 pass): {B, S*W, B} - the B class rows,
+// read and written in place in the [B*S, W] residual stream; row b of the B-row intermediates is image b.  a_rows is what the dgrad
+// GEMMs that read the stream are told about the readable rows of their A operand (0: the default, M rounded up).
+struct Rows { int M; long ld; int a_rows; };
+
 // ---- forward -----------------------------------------------------------------------------------
+// for_peer: the bf16 handle whose backward will read this (saving) forward - the handoff - or null
 template <typename T>
 static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, int normalize, int save,
-                        float* out_emb, hipStream_t s, const TokPass* tp = nullptr) {
+                        float* out_emb, hipStream_t s, const TokPass* tp = nullptr, rvlm_vit* for_peer = nullptr) {
     const int S = h->S, W = h->W, L = h->L, D = h->D, M = B * S, M0 = B * h->G * h->G;
     const int Lrun = tp ? tp->depth : L;            // blocks run
     const bool tail = h->cls_tail && !tp;           // a token pass needs every row of the last block
@@ -536,18 +558,20 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
     // instead of letting a later backward run on a mixture of two passes.
     h->saved_B = 0;
     h->a3_of = nullptr;      // (x3) nothing an earlier enqueue left in the split copy is this pass's operand
-    // a forward FOR a peer (handoff) is a saving forward of an fp32-storage handle; it overwrites the peer's bf16 tensors
+    // a forward FOR a peer (handoff) is a saving forward of an fp32-storage handle on the fp32 flash attention (no probabilities
+    // kept: this handle's own backward is refused for that pass, Saved::ForPeer); it overwrites the peer's bf16 tensors
     // (sequence lengths the flash kernel does not take - S = 577 at 336 px - run the batched attention path as before: the handoff then
     // exports the bf16 tensors itself and takes the log-sum-exp rows the softmax pass wrote, vit_backward_from)
     const bool flash_ok = !h->bf16 && attn_fwd_f32_flash_covers(h->S);
-    rvlm_vit* const peer = (flash_ok && save == 1) ? h->peer : nullptr;
+    FwdPass fp;
+    fp.peer = (flash_ok && save == 1) ? for_peer : nullptr;
+    fp.flash = flash_ok && (h->own_flash || fp.peer != nullptr || (save == 0 && h->flash_inference));
+    rvlm_vit* const peer = fp.peer;
     if (h->provider && save != 0 && !peer)
         return fail(RVLM_ERR_STATE, "forward: this handle was created as a forward provider (trainable = -2): its saving forwards are run "
                                     "for a bf16 handle (rvlm_vit_forward_for, rvlm_pgd_run_mixed_fwd)");
     if (peer) peer->saved_B = 0;
-    h->cur_flash = flash_ok && (h->own_flash || peer != nullptr || (save == 0 && h->flash_inference));
     h->exported_to = 0; h->exported_dact = false;
-    h->cur_qkv_bf = h->cur_o_bf = nullptr; h->cur_dact_out = nullptr;
     {
         PROF("patch_im2col", 0, (double)B * 3 * h->in_h * h->in_w * (delta ? 8 : 4) + (double)M0 * h->Kpad * sizeof(T));
         rc = h->resize ? resize_im2col_normalize<T>(x, delta, B, h->rs_h, h->rs_w, h->P, h->cfg.mean, h->cfg.std, (T*)h->A0, h->Kpad,
@@ -583,6 +607,11 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
         void* ln1o = save == 2 ? h->ln1_out[l] : h->ln_out;     // linear inputs are kept only for wgrad
         void* ln2o = save == 2 ? h->ln2_out[l] : h->ln_out;
         void* gact = save == 2 ? h->g_act_l[l] : h->g_act;
+        // The class-token tail is this block with (a) the steps after the attention on the class rows, (b) Q for the class rows only,
+        // (c) the class query's attention, (e) no LayerNorm-into-split (the tail is bf16 only); its few-row launches are accounted as
+        // two coarse profile classes (tail_attn_fwd, tail_mlp_fwd) instead of one per step.
+        const bool tl = tail && l == L - 1;
+        const Rows r = tl ? Rows{B, (long)S * W, B} : Rows{M, (long)W, 0};      // (a)
         {
             PROF("layernorm_fwd", 0, (double)M * W * (4 + sizeof(T)));
             if (ln_into_split(h, s, x_in, y.ln1_w, y.ln1_b, ln1o, h->mean_at(1 + 2 * l), h->rstd_at(1 + 2 * l), M, 3 * W, &rc)) { if (rc) return rc; }
@@ -590,64 +619,44 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
             if ((rc = layernorm_fwd<T>(x_in, W, y.ln1_w, y.ln1_b, (T*)ln1o, W, h->mean_at(1 + 2 * l),
                                        h->rstd_at(1 + 2 * l), M, W, s))) return rc;
         }
-        if (tail && l == L - 1) {
-            PROF("gemm_qkv_fwd", 2.0 * M * W * 2 * W + 2.0 * B * W * W, 0);
-            if ((rc = qkv_tail_fwd(h, s, ln1o, y, h->qkv[sl], B))) return rc;
-        } else {
-            PROF("gemm_qkv_fwd", 2.0 * M * W * 3 * W, 0);
-            if ((rc = linear_fwd<T>(h, s, ln1o, W, M, 3 * W, W, y.w_in, y.w_in_nk, y.b_in, EPI_BF16,
-                                    h->qkv[sl], 3 * W, nullptr, nullptr))) return rc;
-        }
-        if (tail && l == L - 1) {
-            const long SW = (long)S * W;
-            {
-                PROF("tail_attn_fwd", 4.0 * B * h->H * (double)S * 64, (double)M * 2 * W * sizeof(T));
-                if ((rc = attn_cls_fwd_bf16((const bf16_t*)h->qkv[sl], 3 * W, (bf16_t*)h->attn_o[sl], W, h->lse_cls, B, h->H,
-                                            S, s))) return rc;
-            }
-            {
-                PROF("tail_mlp_fwd", 2.0 * B * W * 9 * W, 0);
-                if ((rc = linear_fwd<T>(h, s, h->attn_o[sl], W, B, W, W, y.w_out, y.w_out_nk, y.b_out, EPI_F32_RESID,
-                                        x_mid, SW, nullptr, x_in))) return rc;
-                if ((rc = layernorm_fwd<T>(x_mid, SW, y.ln2_w, y.ln2_b, (T*)ln2o, W, h->mean_at(2 + 2 * l),
-                                           h->rstd_at(2 + 2 * l), B, W, s))) return rc;
-                if ((rc = linear_fwd<T>(h, s, ln2o, W, B, 4 * W, W, y.w_fc, y.w_fc_nk, y.b_fc, EPI_BF16_ACT,
-                                        gact, 4 * W, save ? h->h_pre[sl] : nullptr, nullptr))) return rc;
-                if ((rc = linear_fwd<T>(h, s, gact, 4 * W, B, W, 4 * W, y.w_proj, y.w_proj_nk, y.b_proj,
-                                        EPI_F32_RESID, x_out, SW, nullptr, x_mid))) return rc;
-            }
-            continue;
-        }
         {
-            PROF("attn_fwd", attn_flops, 0);
-            h->cur_lse2 = (save && !h->lse2.empty()) ? h->lse2[sl] : nullptr;
-            if (peer) { h->cur_qkv_bf = (bf16_t*)peer->qkv[l]; h->cur_o_bf = (bf16_t*)peer->attn_o[l]; }   // (the lse rows stay in h->lse2)
-            if ((rc = attention_fwd<T>(h, s, h->qkv[sl], h->attn_o[sl], h->lse[sl], B))) return rc;
-        }
-        {
-            PROF("gemm_out_fwd", 2.0 * M * W * W, 0);
-            if ((rc = linear_fwd<T>(h, s, h->attn_o[sl], W, M, W, W, y.w_out, y.w_out_nk, y.b_out, EPI_F32_RESID,
-                                    x_mid, W, nullptr, x_in))) return rc;
-        }
-        {
-            PROF("layernorm_fwd", 0, (double)M * W * (4 + sizeof(T)));
-            if (ln_into_split(h, s, x_mid, y.ln2_w, y.ln2_b, ln2o, h->mean_at(2 + 2 * l), h->rstd_at(2 + 2 * l), M, 4 * W, &rc)) { if (rc) return rc; }
-            else
-            if ((rc = layernorm_fwd<T>(x_mid, W, y.ln2_w, y.ln2_b, (T*)ln2o, W, h->mean_at(2 + 2 * l),
-                                       h->rstd_at(2 + 2 * l), M, W, s))) return rc;
-        }
-        {
-            PROF("gemm_fc1_fwd", 2.0 * M * W * 4 * W, 0);
-            h->cur_dact_out = peer ? (bf16_t*)peer->h_pre[l] : nullptr;
-            rc = linear_fwd<T>(h, s, ln2o, W, M, 4 * W, W, y.w_fc, y.w_fc_nk, y.b_fc, EPI_BF16_ACT,
-                               gact, 4 * W, save ? h->h_pre[sl] : nullptr, nullptr);
-            h->cur_dact_out = nullptr;
+            PROF("gemm_qkv_fwd", tl ? 2.0 * M * W * 2 * W + 2.0 * B * W * W : 2.0 * M * W * 3 * W, 0);
+            rc = tl ? qkv_tail_fwd(h, s, ln1o, y, h->qkv[sl], B)      // (b)
+                    : linear_fwd<T>(h, s, ln1o, W, M, 3 * W, W, y.w_in, y.w_in_nk, y.b_in, EPI_BF16, h->qkv[sl], 3 * W, nullptr, nullptr);
             if (rc) return rc;
         }
+        if (tl) {      // (c)
+            PROF("tail_attn_fwd", 4.0 * B * h->H * (double)S * 64, (double)M * 2 * W * sizeof(T));
+            if ((rc = attn_cls_fwd_bf16((const bf16_t*)h->qkv[sl], 3 * W, (bf16_t*)h->attn_o[sl], W, h->lse_cls, B, h->H,
+                                        S, s))) return rc;
+        } else {
+            PROF("attn_fwd", attn_flops, 0);
+            float* lse2 = (save && !h->lse2.empty()) ? h->lse2[sl] : nullptr;      // (with a peer too: the lse rows stay in h->lse2)
+            if ((rc = attention_fwd<T>(h, s, fp, h->qkv[sl], h->attn_o[sl], h->lse[sl], lse2, peer ? (bf16_t*)peer->qkv[l] : nullptr,
+                                       peer ? (bf16_t*)peer->attn_o[l] : nullptr, B))) return rc;
+        }
+        ProfScope tail_mlp(h, s, tl ? "tail_mlp_fwd" : nullptr, 2.0 * B * W * 9 * W, 0);      // (the four launches below, to the end of the block)
         {
-            PROF("gemm_fc2_fwd", 2.0 * M * W * 4 * W, 0);
-            if ((rc = linear_fwd<T>(h, s, gact, 4 * W, M, W, 4 * W, y.w_proj, y.w_proj_nk, y.b_proj,
-                                    EPI_F32_RESID, x_out, W, nullptr, x_mid))) return rc;
+            PROF_IF(!tl, "gemm_out_fwd", 2.0 * M * W * W, 0);
+            if ((rc = linear_fwd<T>(h, s, h->attn_o[sl], W, r.M, W, W, y.w_out, y.w_out_nk, y.b_out, EPI_F32_RESID,
+                                    x_mid, r.ld, nullptr, x_in))) return rc;
+        }
+        {
+            PROF_IF(!tl, "layernorm_fwd", 0, (double)M * W * (4 + sizeof(T)));
+            if (!tl && ln_into_split(h, s, x_mid, y.ln2_w, y.ln2_b, ln2o, h->mean_at(2 + 2 * l), h->rstd_at(2 + 2 * l), M, 4 * W, &rc)) { if (rc) return rc; }      // (e)
+            else
+            if ((rc = layernorm_fwd<T>(x_mid, r.ld, y.ln2_w, y.ln2_b, (T*)ln2o, W, h->mean_at(2 + 2 * l),
+                                       h->rstd_at(2 + 2 * l), r.M, W, s))) return rc;
+        }
+        {
+            PROF_IF(!tl, "gemm_fc1_fwd", 2.0 * M * W * 4 * W, 0);
+            if ((rc = linear_fwd<T>(h, s, ln2o, W, r.M, 4 * W, W, y.w_fc, y.w_fc_nk, y.b_fc, EPI_BF16_ACT, gact, 4 * W,
+                                    save ? h->h_pre[sl] : nullptr, nullptr, 0, peer ? (bf16_t*)peer->h_pre[l] : nullptr))) return rc;
+        }
+        {
+            PROF_IF(!tl, "gemm_fc2_fwd", 2.0 * M * W * 4 * W, 0);
+            if ((rc = linear_fwd<T>(h, s, gact, 4 * W, r.M, W, 4 * W, y.w_proj, y.w_proj_nk, y.b_proj,
+                                    EPI_F32_RESID, x_out, r.ld, nullptr, x_mid))) return rc;
         }
     }
     if (tp) {
@@ -675,13 +684,12 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
             if ((rc = l2_normalize_fwd(h->emb_raw, out_emb, h->inv_norm, B, D, s))) return rc;
         }
     }
-    if (save) { h->saved_B = B; h->saved_norm = normalize != 0; h->saved_mode = save; h->next_param_stage = 0; }
-    if (save && tp) { h->saved_mode = 4; h->saved_depth = Lrun; h->saved_lnpost = tp->ln_post != 0; }
-    if (peer) {      // (saved_mode 3: for the peer's backward only - a provider's single slots / no probabilities kept for a batched backward)
-        if (h->provider || !h->own_flash) h->saved_mode = 3;
+    if (save) { h->saved_B = B; h->saved_norm = normalize != 0; h->saved_mode = (Saved)save; h->next_param_stage = 0; }
+    if (save && tp) { h->saved_mode = Saved::Tokens; h->saved_depth = Lrun; h->saved_lnpost = tp->ln_post != 0; }
+    if (peer) {      // (for the peer's backward only - a provider's single slots / no probabilities kept for a batched backward)
+        if (h->provider || !h->own_flash) h->saved_mode = Saved::ForPeer;
         h->exported_to = peer->uid;
     }
-    h->cur_flash = false; h->cur_qkv_bf = h->cur_o_bf = nullptr; h->cur_lse2 = nullptr;
     return RVLM_OK;
 }
 
@@ -696,174 +704,6 @@ widen_bf16_kernel(const bf16_t* __restrict__ src, float* __restrict__ dst, size_
         *(float4*)(dst + 8 * i) = *(const float4*)&o[0];
         *(float4*)(dst + 8 * i + 4) = *(const float4*)&o[4];
     }
-}
-
-// ---- backward (input gradient only) --------------------------------------------------------------
-template <typename T>
-static int backward_impl(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStream_t s, bool fp32_dres = false,
-                         const TokSeed* ts = nullptr) {
-    const int S = h->S, W = h->W, L = h->L, D = h->D, M = B * S, M0 = B * h->G * h->G;
-    const int Ltop = ts ? ts->depth : L;            // the stream enters above block Ltop - 1
-    const bool tail = h->cls_tail && !ts;
-    const double attn_flops = 8.0 * B * h->H * (double)S * S * 64;
-    constexpr bool LP = !std::is_same<T, float>::value;
-    // the fp32 residual-gradient stream, or none (LayerNorm backward then accumulates in the bf16 buffer, rvlm_vit::lp_dres)
-    float* const dres32 = (LP && h->lp_dres && !fp32_dres) ? nullptr : h->dres;
-    int rc;
-    h->a3_of = nullptr;
-    if (ts) {
-        // token pass: the stream starts as the token cotangent (every row live), plus the pooled path's class rows when d_emb is given
-        PROF("tokens_seed", d_emb ? 2.0 * B * W * D : 0.0, (double)M * W * (4 + (dres32 ? 4 : 0) + (LP ? sizeof(T) : 0)));
-        const long SW = (long)S * W;
-        if (d_emb) {  // d_pooled = d_emb @ proj^T (a token pass's embedding is un-normalised)
-            GemmF32 g;
-            g.A = d_emb; g.sam = D; g.sak = 1;
-            g.B = h->proj; g.sbn = D; g.sbk = 1;
-            g.C = h->d_pooled; g.scm = W; g.scn = 1;
-            g.M = B; g.N = W; g.K = D;
-            if ((rc = gemm_f32(g, s))) return rc;
-        }
-        if (ts->d_tokens && !ts->ln_post) {
-            const float* cls_add = nullptr;
-            if (d_emb) {  // ln_post'(d_pooled) into the class rows of the fp32 buffer (a scratch where the stream is bf16 only): the seed
-                          // kernel adds them in fp32 before it rounds
-                if ((rc = layernorm_bwd<float, float>(h->d_pooled, W, h->xs[2 * L], SW, h->lnpost_w, h->mean_at(2 * L + 1),
-                                                      h->rstd_at(2 * L + 1), h->dres, SW, nullptr, SW, 0, B, W, s))) return rc;
-                cls_add = h->dres;
-            }
-            if ((rc = tokens_seed(ts->d_tokens, cls_add, SW, dres32, LP ? (bf16_t*)h->dres_lp : nullptr, M, h->Mp, S, W, s))) return rc;
-        } else if (ts->d_tokens) {
-            if (h->Mp > M) {
-                if (dres32) RVLM_HIP(hipMemsetAsync(dres32 + (size_t)M * W, 0, (size_t)(h->Mp - M) * W * 4, s));
-                if (LP) RVLM_HIP(hipMemsetAsync((T*)h->dres_lp + (size_t)M * W, 0, (size_t)(h->Mp - M) * W * sizeof(T), s));
-            }
-            if ((rc = layernorm_bwd<float, T>(ts->d_tokens, W, h->xs[2 * Ltop], W, h->lnpost_w, h->tok_mean, h->tok_rstd, dres32, W,
-                                              LP ? (T*)h->dres_lp : nullptr, W, 0, M, W, s))) return rc;
-            if (d_emb && (rc = layernorm_bwd<float, T>(h->d_pooled, W, h->xs[2 * L], SW, h->lnpost_w, h->mean_at(2 * L + 1),
-                                                       h->rstd_at(2 * L + 1), dres32, SW, LP ? (T*)h->dres_lp : nullptr, SW, 1, B, W, s)))
-                return rc;
-        }
-    } else {
-        PROF("head_bwd", 2.0 * B * W * D, 0);
-        const float* d_raw = d_emb;
-        if (h->saved_norm) {
-            if ((rc = l2_normalize_bwd(d_emb, h->emb_raw, h->inv_norm, h->d_raw, B, D, s))) return rc;
-            d_raw = h->d_raw;
-        }
-        GemmF32 g;  // d_pooled = d_raw @ proj^T
-        g.A = d_raw; g.sam = D; g.sak = 1;
-        g.B = h->proj; g.sbn = D; g.sbk = 1;
-        g.C = h->d_pooled; g.scm = W; g.scn = 1;
-        g.M = B; g.N = W; g.K = D;
-        if ((rc = gemm_f32(g, s))) return rc;
-        if (!tail) {   // with the class-token tail the last block's ln_1 backward overwrites the other rows
-            if (dres32) RVLM_HIP(hipMemsetAsync(dres32, 0, (size_t)h->Mp * W * 4, s));
-            if (LP) RVLM_HIP(hipMemsetAsync(h->dres_lp, 0, (size_t)h->Mp * W * sizeof(T), s));
-        }
-        if ((rc = layernorm_bwd<float, T>(h->d_pooled, W, h->xs[2 * L], (long)S * W, h->lnpost_w,
-                                          h->mean_at(2 * L + 1), h->rstd_at(2 * L + 1), dres32, (long)S * W,
-                                          LP ? (T*)h->dres_lp : nullptr, (long)S * W, 0, B, W, s))) return rc;
-    }
-    const void* dres_A = LP ? (const void*)h->dres_lp : (const void*)h->dres;
-    for (int l = Ltop - 1; l >= 0; --l) {
-        Layer& y = h->layers[l];
-        if (tail && l == L - 1) {
-            const long SW = (long)S * W;
-            {
-                PROF("tail_mlp_bwd", 2.0 * B * W * 9 * W, 0);
-                if ((rc = linear_dgrad<T>(h, s, dres_A, SW, B, W, 4 * W, y.w_proj, 4 * W, y.w_proj_t, EPI_BF16_DACT,
-                                          h->dh, 4 * W, h->h_pre[l], B))) return rc;
-                if ((rc = linear_dgrad<T>(h, s, h->dh, 4 * W, B, 4 * W, W, y.w_fc, W, y.w_fc_t, EPI_BF16, h->d_ln, W,
-                                          nullptr))) return rc;
-                if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, h->xs[2 * l + 1], SW, y.ln2_w, h->mean_at(2 + 2 * l),
-                                              h->rstd_at(2 + 2 * l), dres32, SW, (T*)h->dres_lp, SW, 1, B, W, s)))
-                    return rc;
-                if ((rc = linear_dgrad<T>(h, s, dres_A, SW, B, W, W, y.w_out, W, y.w_out_t, EPI_BF16, h->d_o, W,
-                                          nullptr, B))) return rc;
-            }
-            {
-                PROF("tail_attn_bwd", 12.0 * B * h->H * (double)S * 64, (double)M * 5 * W * sizeof(T));
-                if ((rc = attn_cls_bwd_bf16((const bf16_t*)h->qkv[l], 3 * W, (const bf16_t*)h->attn_o[l], W,
-                                            (const bf16_t*)h->d_o, W, h->lse_cls, (bf16_t*)h->dqkv, 3 * W, B, h->H, S, s)))
-                    return rc;
-            }
-        } else {
-        {
-            PROF("gemm_fc2_bwd", 2.0 * M * W * 4 * W, 0);
-            if ((rc = linear_dgrad<T>(h, s, dres_A, W, M, W, 4 * W, y.w_proj, 4 * W, y.w_proj_t, EPI_BF16_DACT,
-                                      h->dh, 4 * W, h->h_pre[l]))) return rc;
-        }
-        {
-            PROF("gemm_fc1_bwd", 2.0 * M * W * 4 * W, 0);
-            if ((rc = linear_dgrad<T>(h, s, h->dh, 4 * W, M, 4 * W, W, y.w_fc, W, y.w_fc_t, EPI_BF16, h->d_ln, W,
-                                      nullptr))) return rc;
-        }
-        {
-            PROF("layernorm_bwd", 0, (double)M * W * ((dres32 ? 12 : 6) + 2 * sizeof(T)));
-            if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, h->xs[2 * l + 1], W, y.ln2_w, h->mean_at(2 + 2 * l),
-                                          h->rstd_at(2 + 2 * l), dres32, W, LP ? (T*)h->dres_lp : nullptr, W, 1,
-                                          M, W, s))) return rc;
-        }
-        {
-            PROF("gemm_out_bwd", 2.0 * M * W * W, 0);
-            if ((rc = linear_dgrad<T>(h, s, dres_A, W, M, W, W, y.w_out, W, y.w_out_t, EPI_BF16, h->d_o, W,
-                                      nullptr))) return rc;
-        }
-        {
-            PROF("attn_bwd", attn_flops, 0);
-            h->cur_lse2 = h->lse2.empty() ? nullptr : h->lse2[l];
-            if ((rc = attention_bwd<T>(h, s, h->qkv[l], h->attn_o[l], h->d_o, h->lse[l], h->dqkv, B))) return rc;
-        }
-        }
-        if (tail && l == L - 1) {
-            PROF("gemm_qkv_bwd", 2.0 * M * W * 2 * W + 2.0 * B * W * 3 * W, 0);
-            if ((rc = qkv_tail_bwd(h, s, h->dqkv, y, h->d_ln, B))) return rc;
-        } else {
-            PROF("gemm_qkv_bwd", 2.0 * M * W * 3 * W, 0);
-            if ((rc = linear_dgrad<T>(h, s, h->dqkv, 3 * W, M, 3 * W, W, y.w_in, W, y.w_in_t, EPI_BF16, h->d_ln, W,
-                                      nullptr))) return rc;
-        }
-        {
-            PROF("layernorm_bwd", 0, (double)M * W * ((dres32 ? 12 : 6) + 2 * sizeof(T)));
-            if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, h->xs[2 * l], W, y.ln1_w, h->mean_at(1 + 2 * l),
-                                          h->rstd_at(1 + 2 * l), dres32, W, LP ? (T*)h->dres_lp : nullptr, W,
-                                          (tail && l == L - 1) ? -S : 1, M, W, s))) return rc;
-        }
-    }
-    {
-        PROF("embed_lnpre_bwd", 0, (double)M * W * 8);
-        if (!dres32) {      // (the embedding backward reads the residual gradient as fp32: one widening pass per backward, 40 us)
-            hipLaunchKernelGGL(widen_bf16_kernel, dim3(ew_blocks((size_t)M * W / 8)), dim3(256), 0, s, (const bf16_t*)h->dres_lp, h->dres, (size_t)M * W / 8);
-            RVLM_CHECK_LAUNCH();
-        }
-        if ((rc = embed_lnpre_bwd<T>(h->dres, W, h->patch_out, W, h->cls, h->pos, h->lnpre_w, h->mean_at(0),
-                                     h->rstd_at(0), (T*)h->d_patch, W, B, S, W, s))) return rc;
-    }
-    {
-        PROF("gemm_patch_bwd", 2.0 * M0 * W * h->Kp, 0);
-        if (h->bf16) {
-            GemmBf16 g;
-            g.A = (const bf16_t*)h->d_patch; g.lda = W; g.Bw = h->conv_t; g.ldb = W;
-            g.M = M0; g.N = h->Kpad; g.K = W; g.a_rows = h->Mp0; g.epi = EPI_F32; g.out = h->dA0; g.ldo = h->Kpad;
-            with_scratch(h, g);
-            rc = gemm_bf16_nt(g, s);
-        } else {
-            GemmF32 g;
-            g.A = (const float*)h->d_patch; g.sam = W; g.sak = 1;
-            g.B = h->conv_f32; g.sbn = 1; g.sbk = h->Kp;
-            g.C = h->dA0; g.scm = h->Kpad; g.scn = 1;
-            g.M = M0; g.N = h->Kp; g.K = W;
-            rc = gemm_f32(g, s);
-        }
-        if (rc) return rc;
-    }
-    {
-        PROF("patch_col2im", 0, (double)B * 3 * h->img * h->img * 4 + (double)B * 3 * h->in_h * h->in_w * 4);
-        rc = h->resize ? col2im_resize_grad<float>(h->dA0, h->Kpad, B, h->rs_h, h->rs_w, h->P, h->cfg.std, grad_x, s)
-                       : col2im_grad<float>(h->dA0, h->Kpad, B, h->img, h->P, h->cfg.std, grad_x, s);
-        if (rc) return rc;
-    }
-    return RVLM_OK;
 }
 
 // ---- weight gradients ------------------------------------------------------------------------------
@@ -932,120 +772,287 @@ int wgrad<float>(rvlm_vit* h, hipStream_t s, const void* dY, long lddy, const vo
     return gemm_f32(g, s);
 }
 
-// Stages of the parameter backward, in execution order: 0 = head (proj, ln_post), 1 + j = transformer block L-1-j,
-// L + 1 = embeddings (ln_pre, positional / class embedding, conv1).  [stage_begin, stage_end) lets the host cut the
-// pass into gradient buckets whose all-reduce overlaps the remaining stages (robustvlm_amd/trainer.py).
-template <typename T>
-static int backward_params_impl(rvlm_vit* h, const float* d_emb, int B, const rvlm_vit_weights* gw, int acc,
-                                int stage_begin, int stage_end, hipStream_t s) {
-    const int S = h->S, W = h->W, L = h->L, D = h->D, M = B * S, M0 = B * h->G * h->G;
-    constexpr bool LP = !std::is_same<T, float>::value;
-    auto G = [](const float* p) { return const_cast<float*>(p); };
+// ---- backward ------------------------------------------------------------------------------------
+// What a backward reads of a SAVED FORWARD, as opposed to what it reads of the handle it runs on (weights, scratch, the bf16
+// qkv / attention output / act'(fc1), and - parameter pass - the kept linear inputs).  A handle's own backward views itself; the
+// handoff (vit_backward_from) views the fp32-storage handle's forward from the bf16 handle's kernels.
+struct SavedView {
+    float* const* xs;                     // 2L+1 residual-stream slots
+    const float *st_mean, *st_rstd;       // LayerNorm statistics, slot i at i * Mp
+    long Mp;
+    const float *patch_out, *emb_raw, *inv_norm;
+    float* const* lse;                    // per block: log-sum-exp rows (bf16 kernels) / probabilities (fp32 batched path)
+    float* const* lse2;                   // per block: the fp32 flash kernels' log-sum-exp rows, or null
+    bool norm;                            // the forward's output was l2-normalised
+    bool tail;                            // its last block ran as the class-token tail
+    const float* mean_at(int i) const { return st_mean + (size_t)i * Mp; }
+    const float* rstd_at(int i) const { return st_rstd + (size_t)i * Mp; }
+};
+static SavedView own_view(const rvlm_vit* h) {
+    return {h->xs.data(), h->st_mean, h->st_rstd, h->Mp, h->patch_out, h->emb_raw, h->inv_norm, h->lse.data(),
+            h->lse2.empty() ? nullptr : h->lse2.data(), h->saved_norm, h->cls_tail};
+}
+
+// Where a backward that also produces the parameter gradients puts them, and which of its stages this call runs.  Stages in
+// execution order: 0 = head (proj, ln_post), 1 + j = transformer block L-1-j, L + 1 = embeddings (ln_pre, positional / class
+// embedding, conv1).  [stage_begin, stage_end) lets the host cut the pass into gradient buckets whose all-reduce overlaps the
+// remaining stages (robustvlm_amd/trainer.py); the stages hand the residual gradient to each other through the handle.
+struct ParamSink { const rvlm_vit_weights* gw; int accumulate, stage_begin, stage_end; };
+static inline float* grad_of(const float* p) { return const_cast<float*>(p); }
+
+// Head, first half: d_raw = l2-normalise'(d_emb) where the forward normalised, [sink: proj gradient], d_pooled = d_raw @ proj^T,
+// [sink: ln_post's gradients].  Leaves h->d_pooled.
+static int head_dpooled(rvlm_vit* h, const SavedView& v, const float* d_emb, int B, const ParamSink* sink, hipStream_t s) {
+    const int W = h->W, L = h->L, D = h->D;
     int rc;
-    const void* dres_A = LP ? (const void*)h->dres_lp : (const void*)h->dres;
-    if (stage_begin <= 0 && stage_end > 0) {
-    // ---- head ----
     const float* d_raw = d_emb;
-    if (h->saved_norm) {
-        if ((rc = l2_normalize_bwd(d_emb, h->emb_raw, h->inv_norm, h->d_raw, B, D, s))) return rc;
+    if (v.norm) {
+        if ((rc = l2_normalize_bwd(d_emb, v.emb_raw, v.inv_norm, h->d_raw, B, D, s))) return rc;
         d_raw = h->d_raw;
     }
-    {   // dproj[W,D] (+)= pooled^T d_raw
+    if (sink) {   // dproj[W,D] (+)= pooled^T d_raw
         GemmF32 g;
         g.A = h->pooled; g.sam = 1; g.sak = W;
         g.B = d_raw; g.sbn = 1; g.sbk = D;
-        g.C = G(gw->proj); g.scm = D; g.scn = 1;
+        g.C = grad_of(sink->gw->proj); g.scm = D; g.scn = 1;
         g.M = W; g.N = D; g.K = B;
-        g.residual = acc ? gw->proj : nullptr;
+        g.residual = sink->accumulate ? sink->gw->proj : nullptr;
         if ((rc = gemm_f32(g, s))) return rc;
     }
-    {   // d_pooled = d_raw @ proj^T
-        GemmF32 g;
-        g.A = d_raw; g.sam = D; g.sak = 1;
-        g.B = h->proj; g.sbn = D; g.sbk = 1;
-        g.C = h->d_pooled; g.scm = W; g.scn = 1;
-        g.M = B; g.N = W; g.K = D;
-        if ((rc = gemm_f32(g, s))) return rc;
+    GemmF32 g;  // d_pooled = d_raw @ proj^T
+    g.A = d_raw; g.sam = D; g.sak = 1;
+    g.B = h->proj; g.sbn = D; g.sbk = 1;
+    g.C = h->d_pooled; g.scm = W; g.scn = 1;
+    g.M = B; g.N = W; g.K = D;
+    if ((rc = gemm_f32(g, s))) return rc;
+    if (sink) return ln_param_grad<float>(h->d_pooled, W, v.xs[2 * L], (long)h->S * W, v.mean_at(2 * L + 1), v.rstd_at(2 * L + 1), B, W,
+                                          grad_of(sink->gw->ln_post_weight), grad_of(sink->gw->ln_post_bias), sink->accumulate,
+                                          h->red_scratch, h->red_floats, s);
+    return RVLM_OK;
+}
+// Head, second half: ln_post'(d_pooled) into the class rows (stride S*W) of d32 and / or dlp, written or added (accumulate).
+template <typename To>
+static int head_lnpost_bwd(rvlm_vit* h, const SavedView& v, float* d32, To* dlp, int accumulate, int B, hipStream_t s) {
+    const long SW = (long)h->S * h->W;
+    return layernorm_bwd<float, To>(h->d_pooled, h->W, v.xs[2 * h->L], SW, h->lnpost_w, v.mean_at(2 * h->L + 1), v.rstd_at(2 * h->L + 1),
+                                    d32, SW, dlp, SW, accumulate, B, h->W, s);
+}
+
+// Embedding stage of the input-gradient pass: ln_pre / embedding backward, patch GEMM, col2im
+template <typename T>
+static int embed_bwd_input(rvlm_vit* h, const SavedView& v, bool widen, int B, float* grad_x, hipStream_t s) {
+    const int S = h->S, W = h->W, M = B * S, M0 = B * h->G * h->G;
+    int rc;
+    {
+        PROF("embed_lnpre_bwd", 0, (double)M * W * 8);
+        if (widen) {      // (the embedding backward reads the residual gradient as fp32: one widening pass per backward, 40 us)
+            hipLaunchKernelGGL(widen_bf16_kernel, dim3(ew_blocks((size_t)M * W / 8)), dim3(256), 0, s, (const bf16_t*)h->dres_lp, h->dres, (size_t)M * W / 8);
+            RVLM_CHECK_LAUNCH();
+        }
+        if ((rc = embed_lnpre_bwd<T>(h->dres, W, v.patch_out, W, h->cls, h->pos, h->lnpre_w, v.mean_at(0),
+                                     v.rstd_at(0), (T*)h->d_patch, W, B, S, W, s))) return rc;
     }
-    if ((rc = ln_param_grad<float>(h->d_pooled, W, h->xs[2 * L], (long)S * W, h->mean_at(2 * L + 1),
-                                   h->rstd_at(2 * L + 1), B, W, G(gw->ln_post_weight), G(gw->ln_post_bias), acc,
-                                   h->red_scratch, h->red_floats, s)))
-        return rc;
-    if (!h->cls_tail) {
-        RVLM_HIP(hipMemsetAsync(h->dres, 0, (size_t)h->Mp * W * 4, s));
-        if (LP) RVLM_HIP(hipMemsetAsync(h->dres_lp, 0, (size_t)h->Mp * W * sizeof(T), s));
+    {
+        PROF("gemm_patch_bwd", 2.0 * M0 * W * h->Kp, 0);
+        if (h->bf16) {
+            GemmBf16 g;
+            g.A = (const bf16_t*)h->d_patch; g.lda = W; g.Bw = h->conv_t; g.ldb = W;
+            g.M = M0; g.N = h->Kpad; g.K = W; g.a_rows = h->Mp0; g.epi = EPI_F32; g.out = h->dA0; g.ldo = h->Kpad;
+            with_scratch(h, g);
+            rc = gemm_bf16_nt(g, s);
+        } else {
+            GemmF32 g;
+            g.A = (const float*)h->d_patch; g.sam = W; g.sak = 1;
+            g.B = h->conv_f32; g.sbn = 1; g.sbk = h->Kp;
+            g.C = h->dA0; g.scm = h->Kpad; g.scn = 1;
+            g.M = M0; g.N = h->Kp; g.K = W;
+            rc = gemm_f32(g, s);
+        }
+        if (rc) return rc;
     }
-    if ((rc = layernorm_bwd<float, T>(h->d_pooled, W, h->xs[2 * L], (long)S * W, h->lnpost_w, h->mean_at(2 * L + 1),
-                                      h->rstd_at(2 * L + 1), h->dres, (long)S * W, LP ? (T*)h->dres_lp : nullptr,
-                                      (long)S * W, 0, B, W, s))) return rc;
+    PROF("patch_col2im", 0, (double)B * 3 * h->img * h->img * 4 + (double)B * 3 * h->in_h * h->in_w * 4);
+    return h->resize ? col2im_resize_grad<float>(h->dA0, h->Kpad, B, h->rs_h, h->rs_w, h->P, h->cfg.std, grad_x, s)
+                     : col2im_grad<float>(h->dA0, h->Kpad, B, h->img, h->P, h->cfg.std, grad_x, s);
+}
+// Embedding stage of the parameter pass: ln_pre, positional / class embedding, conv1
+template <typename T>
+static int embed_bwd_params(rvlm_vit* h, const SavedView& v, const ParamSink& k, int B, hipStream_t s) {
+    const int S = h->S, W = h->W, M = B * S, M0 = B * h->G * h->G, acc = k.accumulate;
+    int rc;
+    if ((rc = ln_param_grad<float>(h->dres, W, h->tokens, W, v.mean_at(0), v.rstd_at(0), M, W, grad_of(k.gw->ln_pre_weight),
+                                   grad_of(k.gw->ln_pre_bias), acc, h->red_scratch, h->red_floats, s))) return rc;
+    if ((rc = layernorm_bwd<float, float>(h->dres, W, h->tokens, W, h->lnpre_w, v.mean_at(0), v.rstd_at(0), h->dtok,
+                                          W, nullptr, W, 0, M, W, s))) return rc;
+    if ((rc = pos_cls_grad(h->dtok, W, B, S, W, grad_of(k.gw->positional_embedding), grad_of(k.gw->class_embedding), acc, s))) return rc;
+    if ((rc = gather_patch_rows<T>(h->dtok, W, B, S, W, (T*)h->d_patch, W, s))) return rc;
+    // conv1.weight [W, 3*P*P] (+)= d_patch^T A0   (A0 has Kpad >= Kp columns; only Kp are weights)
+    return wgrad<T>(h, s, h->d_patch, W, h->A0, h->Kpad, M0, W, h->Kp, grad_of(k.gw->conv1_weight), h->Kp, acc);
+}
+
+// The backward walker: head (or token seed), blocks from the top down, embeddings - on h's kernels, scratch and weights, of the saved
+// forward `v`.  Without a sink: the input gradient into grad_x.  With a sink: the parameter pass - the same chain with each linear's
+// weight gradient issued before its dgrad and each LayerNorm's before its backward, from the inputs a save-mode-2 forward kept on h
+// (ln1_out, ln2_out, g_act_l, tokens), cut into the sink's stages, always on the fp32 residual-gradient stream, and WITHOUT profile
+// scopes (a training step's classes are not part of rvlm_vit_get_profile).
+// fp32_dres: keep the fp32 stream where the handle would run the bf16-only one (rvlm_vit::lp_dres).
+template <typename T>
+static int backward_impl(rvlm_vit* h, const SavedView& v, const float* d_emb, int B, float* grad_x, hipStream_t s, bool fp32_dres = false,
+                         const TokSeed* ts = nullptr, const ParamSink* sink = nullptr) {
+    const int S = h->S, W = h->W, L = h->L, D = h->D, M = B * S;
+    const int Ltop = ts ? ts->depth : L;            // the stream enters above block Ltop - 1
+    const bool tail = v.tail && !ts;
+    const bool prof = !sink;
+    const int st0 = sink ? sink->stage_begin : 0, st1 = sink ? sink->stage_end : L + 2;
+    const int acc = sink ? sink->accumulate : 0;
+    const double attn_flops = 8.0 * B * h->H * (double)S * S * 64;
+    constexpr bool LP = !std::is_same<T, float>::value;
+    // the fp32 residual-gradient stream, or none (LayerNorm backward then accumulates in the bf16 buffer, rvlm_vit::lp_dres)
+    float* const dres32 = (LP && h->lp_dres && !fp32_dres && !sink) ? nullptr : h->dres;
+    T* const dres_lp = LP ? (T*)h->dres_lp : nullptr;
+    int rc;
+    h->a3_of = nullptr;
+    if (ts) {
+        // token pass: the stream starts as the token cotangent (every row live), plus the pooled path's class rows when d_emb is given
+        PROF("tokens_seed", d_emb ? 2.0 * B * W * D : 0.0, (double)M * W * (4 + (dres32 ? 4 : 0) + (LP ? sizeof(T) : 0)));
+        if (d_emb && (rc = head_dpooled(h, v, d_emb, B, nullptr, s))) return rc;      // (a token pass's embedding is un-normalised)
+        if (ts->d_tokens && !ts->ln_post) {
+            const float* cls_add = nullptr;
+            if (d_emb) {  // ln_post'(d_pooled) into the class rows of the fp32 buffer (a scratch where the stream is bf16 only): the seed
+                          // kernel adds them in fp32 before it rounds
+                if ((rc = head_lnpost_bwd<float>(h, v, h->dres, nullptr, 0, B, s))) return rc;
+                cls_add = h->dres;
+            }
+            if ((rc = tokens_seed(ts->d_tokens, cls_add, (long)S * W, dres32, LP ? (bf16_t*)h->dres_lp : nullptr, M, h->Mp, S, W, s))) return rc;
+        } else if (ts->d_tokens) {
+            if (h->Mp > M) {
+                if (dres32) RVLM_HIP(hipMemsetAsync(dres32 + (size_t)M * W, 0, (size_t)(h->Mp - M) * W * 4, s));
+                if (LP) RVLM_HIP(hipMemsetAsync((T*)h->dres_lp + (size_t)M * W, 0, (size_t)(h->Mp - M) * W * sizeof(T), s));
+            }
+            if ((rc = layernorm_bwd<float, T>(ts->d_tokens, W, v.xs[2 * Ltop], W, h->lnpost_w, h->tok_mean, h->tok_rstd, dres32, W,
+                                              dres_lp, W, 0, M, W, s))) return rc;
+            if (d_emb && (rc = head_lnpost_bwd<T>(h, v, dres32, dres_lp, 1, B, s))) return rc;
+        }
+    } else if (st0 <= 0 && st1 > 0) {
+        PROF_IF(prof, "head_bwd", 2.0 * B * W * D, 0);
+        if ((rc = head_dpooled(h, v, d_emb, B, sink, s))) return rc;
+        if (!tail) {   // with the class-token tail the last block's ln_1 backward overwrites the other rows
+            if (dres32) RVLM_HIP(hipMemsetAsync(dres32, 0, (size_t)h->Mp * W * 4, s));
+            if (LP) RVLM_HIP(hipMemsetAsync(h->dres_lp, 0, (size_t)h->Mp * W * sizeof(T), s));
+        }
+        if ((rc = head_lnpost_bwd<T>(h, v, dres32, dres_lp, 0, B, s))) return rc;
     }
-    for (int l = L - 1; l >= 0; --l) {
-        if (L - l < stage_begin || L - l >= stage_end) continue;
+    const void* dres_A = LP ? (const void*)h->dres_lp : (const void*)h->dres;
+    for (int l = Ltop - 1; l >= 0; --l) {
+        if (L - l < st0 || L - l >= st1) continue;
         Layer& y = h->layers[l];
-        const rvlm_vit_block_weights& gb = gw->blocks_host[l];
-        // last block with the class-token tail: only the B class-token rows are live from here up to the attention
-        const bool tail = h->cls_tail && l == L - 1;
-        const int Mr = tail ? B : M, ar = tail ? B : 0;
-        const long ldr = tail ? (long)S * W : (long)W;
-        // fc2 (c_proj): dY = d(residual), X = act(fc1)
-        if ((rc = wgrad<T>(h, s, dres_A, ldr, h->g_act_l[l], 4 * W, Mr, W, 4 * W, G(gb.mlp_c_proj_weight), 4 * W, acc,
-                           G(gb.mlp_c_proj_bias)))) return rc;
-        if ((rc = linear_dgrad<T>(h, s, dres_A, ldr, Mr, W, 4 * W, y.w_proj, 4 * W, y.w_proj_t, EPI_BF16_DACT, h->dh,
-                                  4 * W, h->h_pre[l], ar))) return rc;
-        // fc1 (c_fc)
-        if ((rc = wgrad<T>(h, s, h->dh, 4 * W, h->ln2_out[l], W, Mr, 4 * W, W, G(gb.mlp_c_fc_weight), W, acc,
-                           G(gb.mlp_c_fc_bias)))) return rc;
-        if ((rc = linear_dgrad<T>(h, s, h->dh, 4 * W, Mr, 4 * W, W, y.w_fc, W, y.w_fc_t, EPI_BF16, h->d_ln, W, nullptr)))
-            return rc;
-        if ((rc = ln_param_grad<T>((const T*)h->d_ln, W, h->xs[2 * l + 1], ldr, h->mean_at(2 + 2 * l),
-                                   h->rstd_at(2 + 2 * l), Mr, W, G(gb.ln_2_weight), G(gb.ln_2_bias), acc,
-                                   h->red_scratch, h->red_floats, s))) return rc;
-        if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, h->xs[2 * l + 1], ldr, y.ln2_w, h->mean_at(2 + 2 * l),
-                                      h->rstd_at(2 + 2 * l), h->dres, ldr, LP ? (T*)h->dres_lp : nullptr, ldr, 1, Mr, W, s)))
-            return rc;
-        // attention out-proj
-        if ((rc = wgrad<T>(h, s, dres_A, ldr, h->attn_o[l], W, Mr, W, W, G(gb.attn_out_proj_weight), W, acc,
-                           G(gb.attn_out_proj_bias)))) return rc;
-        if ((rc = linear_dgrad<T>(h, s, dres_A, ldr, Mr, W, W, y.w_out, W, y.w_out_t, EPI_BF16, h->d_o, W, nullptr, ar)))
-            return rc;
-        if (tail) {
+        const rvlm_vit_block_weights* gb = sink ? &sink->gw->blocks_host[l] : nullptr;
+        // The class-token tail is this block with (a) the steps before the attention (in backward order) on the class rows, (b) the
+        // QKV dgrad over K, V of every row and Q of the class rows, (c) the class query's attention backward, (d) an ln_1 backward that
+        // overwrites the rows that carry no residual gradient yet; its few-row launches are accounted as two coarse profile classes
+        // (tail_mlp_bwd, tail_attn_bwd) instead of one per step.
+        const bool tl = tail && l == L - 1;
+        const Rows r = tl ? Rows{B, (long)S * W, B} : Rows{M, (long)W, 0};      // (a)
+        const bool pf = prof && !tl;
+        {
+            ProfScope tail_mlp(h, s, (prof && tl) ? "tail_mlp_bwd" : nullptr, 2.0 * B * W * 9 * W, 0);      // (the four dgrad / LayerNorm launches)
+            {   // fc2 (c_proj): dY = d(residual), X = act(fc1)
+                PROF_IF(pf, "gemm_fc2_bwd", 2.0 * M * W * 4 * W, 0);
+                if (sink && (rc = wgrad<T>(h, s, dres_A, r.ld, h->g_act_l[l], 4 * W, r.M, W, 4 * W, grad_of(gb->mlp_c_proj_weight), 4 * W, acc,
+                                           grad_of(gb->mlp_c_proj_bias)))) return rc;
+                if ((rc = linear_dgrad<T>(h, s, dres_A, r.ld, r.M, W, 4 * W, y.w_proj, 4 * W, y.w_proj_t, EPI_BF16_DACT,
+                                          h->dh, 4 * W, h->h_pre[l], r.a_rows))) return rc;
+            }
+            {   // fc1 (c_fc)  (its A operand is the B-row dh, not the stream: no a_rows)
+                PROF_IF(pf, "gemm_fc1_bwd", 2.0 * M * W * 4 * W, 0);
+                if (sink && (rc = wgrad<T>(h, s, h->dh, 4 * W, h->ln2_out[l], W, r.M, 4 * W, W, grad_of(gb->mlp_c_fc_weight), W, acc,
+                                           grad_of(gb->mlp_c_fc_bias)))) return rc;
+                if ((rc = linear_dgrad<T>(h, s, h->dh, 4 * W, r.M, 4 * W, W, y.w_fc, W, y.w_fc_t, EPI_BF16, h->d_ln, W,
+                                          nullptr))) return rc;
+            }
+            {
+                PROF_IF(pf, "layernorm_bwd", 0, (double)M * W * ((dres32 ? 12 : 6) + 2 * sizeof(T)));
+                if (sink && (rc = ln_param_grad<T>((const T*)h->d_ln, W, v.xs[2 * l + 1], r.ld, v.mean_at(2 + 2 * l), v.rstd_at(2 + 2 * l),
+                                                   r.M, W, grad_of(gb->ln_2_weight), grad_of(gb->ln_2_bias), acc, h->red_scratch,
+                                                   h->red_floats, s))) return rc;
+                if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, v.xs[2 * l + 1], r.ld, y.ln2_w, v.mean_at(2 + 2 * l),
+                                              v.rstd_at(2 + 2 * l), dres32, r.ld, dres_lp, r.ld, 1, r.M, W, s))) return rc;
+            }
+            {   // attention out-proj
+                PROF_IF(pf, "gemm_out_bwd", 2.0 * M * W * W, 0);
+                if (sink && (rc = wgrad<T>(h, s, dres_A, r.ld, h->attn_o[l], W, r.M, W, W, grad_of(gb->attn_out_proj_weight), W, acc,
+                                           grad_of(gb->attn_out_proj_bias)))) return rc;
+                if ((rc = linear_dgrad<T>(h, s, dres_A, r.ld, r.M, W, W, y.w_out, W, y.w_out_t, EPI_BF16, h->d_o, W,
+                                          nullptr, r.a_rows))) return rc;
+            }
+        }
+        if (tl) {      // (c)
+            PROF_IF(prof, "tail_attn_bwd", 12.0 * B * h->H * (double)S * 64, (double)M * 5 * W * sizeof(T));
             if ((rc = attn_cls_bwd_bf16((const bf16_t*)h->qkv[l], 3 * W, (const bf16_t*)h->attn_o[l], W,
                                         (const bf16_t*)h->d_o, W, h->lse_cls, (bf16_t*)h->dqkv, 3 * W, B, h->H, S, s)))
                 return rc;
         } else {
-            h->cur_lse2 = h->lse2.empty() ? nullptr : h->lse2[l];
-            if ((rc = attention_bwd<T>(h, s, h->qkv[l], h->attn_o[l], h->d_o, h->lse[l], h->dqkv, B))) return rc;
+            PROF_IF(prof, "attn_bwd", attn_flops, 0);
+            if ((rc = attention_bwd<T>(h, s, h->qkv[l], h->attn_o[l], h->d_o, v.lse[l], v.lse2 ? v.lse2[l] : nullptr, h->dqkv, B)))
+                return rc;
         }
-        // qkv in-proj
-        if ((rc = wgrad<T>(h, s, h->dqkv, 3 * W, h->ln1_out[l], W, M, 3 * W, W, G(gb.attn_in_proj_weight), W, acc,
-                           G(gb.attn_in_proj_bias)))) return rc;
-        if ((rc = linear_dgrad<T>(h, s, h->dqkv, 3 * W, M, 3 * W, W, y.w_in, W, y.w_in_t, EPI_BF16, h->d_ln, W, nullptr)))
-            return rc;
-        if ((rc = ln_param_grad<T>((const T*)h->d_ln, W, h->xs[2 * l], W, h->mean_at(1 + 2 * l), h->rstd_at(1 + 2 * l),
-                                   M, W, G(gb.ln_1_weight), G(gb.ln_1_bias), acc, h->red_scratch, h->red_floats, s)))
-            return rc;
-        if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, h->xs[2 * l], W, y.ln1_w, h->mean_at(1 + 2 * l),
-                                      h->rstd_at(1 + 2 * l), h->dres, W, LP ? (T*)h->dres_lp : nullptr, W,
-                                      tail ? -S : 1, M, W, s)))
-            return rc;
+        {   // qkv in-proj  (b: the parameter pass takes the plain dgrad on the tail too, next to its weight gradient over every row)
+            const bool qkv_tail = tl && !sink;
+            PROF_IF(prof, "gemm_qkv_bwd", qkv_tail ? 2.0 * M * W * 2 * W + 2.0 * B * W * 3 * W : 2.0 * M * W * 3 * W, 0);
+            if (sink && (rc = wgrad<T>(h, s, h->dqkv, 3 * W, h->ln1_out[l], W, M, 3 * W, W, grad_of(gb->attn_in_proj_weight), W, acc,
+                                       grad_of(gb->attn_in_proj_bias)))) return rc;
+            rc = qkv_tail ? qkv_tail_bwd(h, s, h->dqkv, y, h->d_ln, B)
+                          : linear_dgrad<T>(h, s, h->dqkv, 3 * W, M, 3 * W, W, y.w_in, W, y.w_in_t, EPI_BF16, h->d_ln, W, nullptr);
+            if (rc) return rc;
+        }
+        {
+            PROF_IF(prof, "layernorm_bwd", 0, (double)M * W * ((dres32 ? 12 : 6) + 2 * sizeof(T)));
+            if (sink && (rc = ln_param_grad<T>((const T*)h->d_ln, W, v.xs[2 * l], W, v.mean_at(1 + 2 * l), v.rstd_at(1 + 2 * l), M, W,
+                                               grad_of(gb->ln_1_weight), grad_of(gb->ln_1_bias), acc, h->red_scratch, h->red_floats, s)))
+                return rc;
+            if ((rc = layernorm_bwd<T, T>((const T*)h->d_ln, W, v.xs[2 * l], W, y.ln1_w, v.mean_at(1 + 2 * l), v.rstd_at(1 + 2 * l),
+                                          dres32, W, dres_lp, W, tl ? -S : 1, M, W, s))) return rc;      // (d)
+        }
     }
-    if (stage_end <= L + 1) return RVLM_OK;
-    // ---- embeddings: ln_pre, positional / class embedding, conv1 ----
-    if ((rc = ln_param_grad<float>(h->dres, W, h->tokens, W, h->mean_at(0), h->rstd_at(0), M, W, G(gw->ln_pre_weight),
-                                   G(gw->ln_pre_bias), acc, h->red_scratch, h->red_floats, s))) return rc;
-    if ((rc = layernorm_bwd<float, float>(h->dres, W, h->tokens, W, h->lnpre_w, h->mean_at(0), h->rstd_at(0), h->dtok,
-                                          W, nullptr, W, 0, M, W, s))) return rc;
-    if ((rc = pos_cls_grad(h->dtok, W, B, S, W, G(gw->positional_embedding), G(gw->class_embedding), acc, s))) return rc;
-    if ((rc = gather_patch_rows<T>(h->dtok, W, B, S, W, (T*)h->d_patch, W, s))) return rc;
-    // conv1.weight [W, 3*P*P] (+)= d_patch^T A0   (A0 has Kpad >= Kp columns; only Kp are weights)
-    if ((rc = wgrad<T>(h, s, h->d_patch, W, h->A0, h->Kpad, M0, W, h->Kp, G(gw->conv1_weight), h->Kp, acc))) return rc;
+    if (st1 <= L + 1) return RVLM_OK;
+    return sink ? embed_bwd_params<T>(h, v, *sink, B, s) : embed_bwd_input<T>(h, v, dres32 == nullptr, B, grad_x, s);
+}
+
+// Which backward may read which saved forward.  A pooled forward the handle kept for itself (Input, or Params: a superset) is read by
+// the input-gradient backward; only Params by the parameter pass; only a token pass by the token backward; the handoff takes any
+// pooled pass of the fp32-storage handle (its own, or one run for the peer).
+// (Input is checked by vit_backward for every caller; only rvlm_vit_backward_input can arrive there without a forward of its own.)
+enum class Reader { Input, Params, Tokens, Handoff };
+static int saved_check(const rvlm_vit* h, Reader r, int B, const char* who = "") {
+    const bool have = B > 0 && h->saved_B == B;
+    const Saved m = h->saved_mode;
+    switch (r) {
+    case Reader::Input:
+        if (!have) return fail(RVLM_ERR_STATE, "rvlm_vit_backward_input: no saved forward for this batch size");
+        if (m == Saved::ForPeer) return fail(RVLM_ERR_STATE, "backward: the saved forward was run for another handle's backward (no probabilities kept)");
+        if (m == Saved::Tokens) return fail(RVLM_ERR_STATE, "backward: the saved forward is a token pass (rvlm_vit_backward_input_tokens differentiates it)");
+        break;
+    case Reader::Params:
+        if (!have || m != Saved::Params) return fail(RVLM_ERR_STATE, std::string(who) + ": needs a forward with save_for_backward == 2 for this batch");
+        break;
+    case Reader::Tokens:
+        if (!have || m != Saved::Tokens)
+            return fail(RVLM_ERR_STATE, h->saved_B > 0 && m != Saved::Tokens
+                            ? "rvlm_vit_backward_input_tokens: the saved forward is a pooled pass (rvlm_vit_backward_input differentiates it)"
+                            : "rvlm_vit_backward_input_tokens: no saved token forward for this batch size");
+        break;
+    case Reader::Handoff:
+        if (!have) return fail(RVLM_ERR_STATE, "handoff: no saved forward for this batch size on the fp32-storage handle");
+        if (m == Saved::Tokens) return fail(RVLM_ERR_STATE, "handoff: the saved forward is a token pass (the handoff precisions take pooled passes only)");
+        break;
+    }
     return RVLM_OK;
 }
 
+// for_peer: see forward_impl
 static int vit_forward(rvlm_vit* h, const float* x, const float* delta, int B, int normalize, int save,
-                       float* out_emb, hipStream_t s) {
-    return h->bf16 ? forward_impl<bf16_t>(h, x, delta, B, normalize, save, out_emb, s)
-                   : forward_impl<float>(h, x, delta, B, normalize, save, out_emb, s);
+                       float* out_emb, hipStream_t s, rvlm_vit* for_peer = nullptr) {
+    return h->bf16 ? forward_impl<bf16_t>(h, x, delta, B, normalize, save, out_emb, s, nullptr, for_peer)
+                   : forward_impl<float>(h, x, delta, B, normalize, save, out_emb, s, nullptr, for_peer);
 }
 static int vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, int B, const TokPass& tp, int save, float* out_emb,
                               hipStream_t s) {
@@ -1053,12 +1060,16 @@ static int vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, i
                    : forward_impl<float>(h, x, delta, B, 0, save, out_emb, s, &tp);
 }
 static int vit_backward_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int B, float* grad_x, hipStream_t s) {
-    return h->bf16 ? backward_impl<bf16_t>(h, d_emb, B, grad_x, s, false, &ts) : backward_impl<float>(h, d_emb, B, grad_x, s, false, &ts);
+    return h->bf16 ? backward_impl<bf16_t>(h, own_view(h), d_emb, B, grad_x, s, false, &ts)
+                   : backward_impl<float>(h, own_view(h), d_emb, B, grad_x, s, false, &ts);
 }
 static int vit_backward(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStream_t s) {
-    if (h->saved_mode == 3) return fail(RVLM_ERR_STATE, "backward: the saved forward was run for another handle's backward (no probabilities kept)");
-    if (h->saved_mode == 4) return fail(RVLM_ERR_STATE, "backward: the saved forward is a token pass (rvlm_vit_backward_input_tokens differentiates it)");
-    return h->bf16 ? backward_impl<bf16_t>(h, d_emb, B, grad_x, s) : backward_impl<float>(h, d_emb, B, grad_x, s);
+    int rc = saved_check(h, Reader::Input, B); if (rc) return rc;
+    return h->bf16 ? backward_impl<bf16_t>(h, own_view(h), d_emb, B, grad_x, s) : backward_impl<float>(h, own_view(h), d_emb, B, grad_x, s);
+}
+static int vit_backward_params(rvlm_vit* h, const float* d_emb, int B, const ParamSink& sink, hipStream_t s) {
+    return h->bf16 ? backward_impl<bf16_t>(h, own_view(h), d_emb, B, nullptr, s, true, nullptr, &sink)
+                   : backward_impl<float>(h, own_view(h), d_emb, B, nullptr, s, true, nullptr, &sink);
 }
 
 // HANDOFF (round 6): the input gradient of the forward SAVED ON `hx` (an fp32-storage handle: x3 or fp32 precision) evaluated by the
@@ -1067,20 +1078,18 @@ static int vit_backward(rvlm_vit* h, const float* d_emb, int B, float* grad_x, h
 // cotangent's way back through the network only meets relative rounding errors (oracle/split_bf16_emulation.py: split-bf16 forward +
 // bf16 backward 0.998 first-step sign agreement with the fp32 oracle; split-bf16 both ways 0.9996; bf16 both ways 0.82).  What the
 // bf16 backward reads as fp32 (residual stream, LayerNorm statistics, patch embeddings, the unnormalised output) it reads from hx's
-// buffers in place (pointers swapped for the duration of the enqueue); what it reads in bf16 (qkv, attention output, act'(fc1)) is
-// exported here from the fp32 tensors hx kept; the log-sum-exp rows were written by hx's softmax pass in the flash kernels' convention.
-// The class-token tail is switched off for this pass (hx ran the last block on every row).
+// buffers in place (the SavedView of hx's forward); what it reads in bf16 (qkv, attention output, act'(fc1)) is exported here from the
+// fp32 tensors hx kept; the log-sum-exp rows were written by hx's softmax pass in the flash kernels' convention.  The view carries no
+// class-token tail (hx ran the last block on every row) and the pass keeps the fp32 residual-gradient stream.
 static int vit_backward_from(rvlm_vit* hb, rvlm_vit* hx, const float* d_emb, int B, float* grad_x, hipStream_t s) {
     if (!hb->bf16 || hx->bf16) return fail(RVLM_ERR_STATE, "handoff: needs a bf16 handle and an fp32-storage (fp32 / x3) handle");
-    if (hx->saved_B != B || B <= 0) return fail(RVLM_ERR_STATE, "handoff: no saved forward for this batch size on the fp32-storage handle");
-    if (hx->saved_mode == 4) return fail(RVLM_ERR_STATE, "handoff: the saved forward is a token pass (the handoff precisions take pooled passes only)");
+    int rc = saved_check(hx, Reader::Handoff, B); if (rc) return rc;
     if (hx->lse2.empty() || hb->inference_only) return fail(RVLM_ERR_STATE, "handoff: inference-only handle");
     if (hb->Mp != hx->Mp || hb->Mp0 != hx->Mp0 || hb->W != hx->W || hb->L != hx->L || hb->S != hx->S || hb->H != hx->H ||
         hb->D != hx->D || hb->P != hx->P || hb->cfg.act != hx->cfg.act)
         return fail(RVLM_ERR_STATE, "handoff: the two handles must hold the same architecture and max_batch");
     rvlm_vit* h = hb;                      // (PROF accounts on the bf16 handle)
     const int W = hb->W, L = hb->L, M = B * hb->S;
-    int rc;
     {
         PROF("handoff_export", 0, (double)M * W * (3 * 6 + 6 + 4 * 6) * L);
         const bool have_qo = hx->exported_to == hb->uid, have_dact = have_qo && hx->exported_dact;     // written by the forward itself
@@ -1092,21 +1101,9 @@ static int vit_backward_from(rvlm_vit* hb, rvlm_vit* hx, const float* d_emb, int
             if (!have_dact && (rc = x3_export_bf16((const float*)hx->h_pre[l], 4 * W, (bf16_t*)hb->h_pre[l], 4 * W, M, 4 * W, hb->cfg.act, 1, s))) return rc;
         }
     }
-    struct Swap {      // hb reads hx's fp32 state in place; restored on every exit path
-        rvlm_vit *a, *b;
-        Swap(rvlm_vit* a_, rvlm_vit* b_) : a(a_), b(b_) { swap(); }
-        ~Swap() { swap(); }
-        void swap() {
-            std::swap(a->xs, b->xs); std::swap(a->st_mean, b->st_mean); std::swap(a->st_rstd, b->st_rstd);
-            std::swap(a->patch_out, b->patch_out); std::swap(a->emb_raw, b->emb_raw); std::swap(a->inv_norm, b->inv_norm);
-            std::swap(a->lse, b->lse2);
-        }
-    } swapped(hb, hx);
-    const bool tail = hb->cls_tail;
-    const bool sn = hb->saved_norm;
-    hb->cls_tail = false; hb->saved_norm = hx->saved_norm;
-    rc = backward_impl<bf16_t>(hb, d_emb, B, grad_x, s, /*fp32_dres=*/true);
-    hb->cls_tail = tail; hb->saved_norm = sn;
+    SavedView v = own_view(hx);      // ... read by the bf16 kernels: the flash-convention rows as their lse, every row of the last block
+    v.lse = hx->lse2.data(); v.lse2 = nullptr; v.tail = false;
+    rc = backward_impl<bf16_t>(hb, v, d_emb, B, grad_x, s, /*fp32_dres=*/true);
     hb->saved_B = 0;        // (hb's own saved forward, if any, lost its bf16 tensors to the exports)
     return rc;
 }
@@ -1338,8 +1335,6 @@ extern "C" int rvlm_vit_forward(rvlm_vit* h, const float* x, const float* delta,
 extern "C" int rvlm_vit_backward_input(rvlm_vit* h, const float* d_emb, int B, float* grad_x,
                                        rvlm_stream_t stream) {
     RVLM_REQUIRE(h && d_emb && grad_x, "rvlm_vit_backward_input: null argument");
-    if (h->saved_B != B || B <= 0)
-        return fail(RVLM_ERR_STATE, "rvlm_vit_backward_input: no saved forward for this batch size");
     return vit_backward(h, d_emb, B, grad_x, (hipStream_t)stream);
 }
 
@@ -1385,10 +1380,7 @@ extern "C" int rvlm_vit_forward_for(rvlm_vit* h, rvlm_vit* consumer, const float
                  h->W == consumer->W && h->L == consumer->L && h->S == consumer->S && h->H == consumer->H,
                  "rvlm_vit_forward_for: needs an fp32-storage handle and a bf16 handle of the same architecture and max_batch");
     RVLM_REQUIRE_SAME_INPUT(h, consumer, "rvlm_vit_forward_for");
-    h->peer = consumer;
-    const int rc = vit_forward(h, x, delta, B, output_normalize, 1, out_emb, (hipStream_t)stream);
-    h->peer = nullptr;
-    return rc;
+    return vit_forward(h, x, delta, B, output_normalize, 1, out_emb, (hipStream_t)stream, consumer);
 }
 
 extern "C" int rvlm_vit_backward_input_from(rvlm_vit* h, rvlm_vit* h_saved, const float* d_emb, int B, float* grad_x,
@@ -1402,20 +1394,16 @@ extern "C" int rvlm_vit_backward_params(rvlm_vit* h, const float* d_emb, int B, 
                                         int accumulate, rvlm_stream_t stream) {
     RVLM_REQUIRE(h && d_emb && grads && grads->blocks_host, "rvlm_vit_backward_params: null argument");
     if (!h->trainable) return fail(RVLM_ERR_STATE, "rvlm_vit_backward_params: handle was not created trainable");
-    if (h->saved_B != B || B <= 0 || h->saved_mode != 2)
-        return fail(RVLM_ERR_STATE, "rvlm_vit_backward_params: needs a forward with save_for_backward == 2 for this batch");
-    hipStream_t s = (hipStream_t)stream;
+    int rc = saved_check(h, Reader::Params, B, "rvlm_vit_backward_params"); if (rc) return rc;
     h->next_param_stage = h->L + 2;
-    return h->bf16 ? backward_params_impl<bf16_t>(h, d_emb, B, grads, accumulate, 0, h->L + 2, s)
-                   : backward_params_impl<float>(h, d_emb, B, grads, accumulate, 0, h->L + 2, s);
+    return vit_backward_params(h, d_emb, B, ParamSink{grads, accumulate, 0, h->L + 2}, (hipStream_t)stream);
 }
 
 extern "C" int rvlm_vit_backward_params_stages(rvlm_vit* h, const float* d_emb, int B, const rvlm_vit_weights* grads,
                                                int accumulate, int stage_begin, int stage_end, rvlm_stream_t stream) {
     RVLM_REQUIRE(h && d_emb && grads && grads->blocks_host, "rvlm_vit_backward_params_stages: null argument");
     if (!h->trainable) return fail(RVLM_ERR_STATE, "rvlm_vit_backward_params_stages: handle was not created trainable");
-    if (h->saved_B != B || B <= 0 || h->saved_mode != 2)
-        return fail(RVLM_ERR_STATE, "rvlm_vit_backward_params_stages: needs a forward with save_for_backward == 2 for this batch");
+    int rc = saved_check(h, Reader::Params, B, "rvlm_vit_backward_params_stages"); if (rc) return rc;
     RVLM_REQUIRE(stage_begin >= 0 && stage_begin < stage_end && stage_end <= h->L + 2,
                  "rvlm_vit_backward_params_stages: need 0 <= stage_begin < stage_end <= layers + 2");
     // stages of one backward hand the residual gradient to each other through the handle: stage k reads what stage
@@ -1424,9 +1412,7 @@ extern "C" int rvlm_vit_backward_params_stages(rvlm_vit* h, const float* d_emb, 
     if (stage_begin != 0 && stage_begin != h->next_param_stage)
         return fail(RVLM_ERR_STATE, "rvlm_vit_backward_params_stages: stages of one backward must run in order from 0 "
                                     "(stage_begin does not continue the previous call's stage_end)");
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = h->bf16 ? backward_params_impl<bf16_t>(h, d_emb, B, grads, accumulate, stage_begin, stage_end, s)
-                           : backward_params_impl<float>(h, d_emb, B, grads, accumulate, stage_begin, stage_end, s);
+    rc = vit_backward_params(h, d_emb, B, ParamSink{grads, accumulate, stage_begin, stage_end}, (hipStream_t)stream);
     h->next_param_stage = rc == RVLM_OK ? stage_end : -1;
     return rc;
 }
@@ -1504,12 +1490,22 @@ static int pgd_run_impl(rvlm_vit* h, const Step& step, const float* x, const flo
 
 int PooledStep::operator()(int it, const float* x, const float* delta, int B, float* lsc, float* grad, hipStream_t s) const {
     rvlm_vit* m = (hf && it < n_first) ? hf : h;
-    if (handoff && m != h) m->peer = h;      // (the forward then writes h's bf16 tensors itself and keeps no probabilities)
-    int rc = vit_forward(m, x, delta, B, loss->output_normalize, 1, m->emb, s);
-    m->peer = nullptr;
+    // (a handoff iteration's forward runs FOR h: it writes h's bf16 tensors itself and keeps no probabilities)
+    int rc = vit_forward(m, x, delta, B, loss->output_normalize, 1, m->emb, s, (handoff && m != h) ? h : nullptr);
     if (rc) return rc;
     if ((rc = loss_step(m, loss, B, loss->reduction, lsc, nullptr, s))) return rc;
     return (handoff && m != h) ? vit_backward_from(h, m, m->d_emb, B, grad, s) : vit_backward(m, m->d_emb, B, grad, s);
+}
+
+// The norm / batch / iteration checks of the perturbation loops' entries, under the entry's name (hf: the second handle of a mixed
+// loop; h == null: the entry has a batch rule of its own)
+static int pgd_loop_check(const std::string& who, int norm_kind, int iterations, int n_first, int B, const rvlm_vit* h,
+                          const rvlm_vit* hf = nullptr) {
+    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, who + ": norm must be L-inf (0) or L2 (2)");
+    if (h && !(B > 1 && B <= h->maxB && (!hf || B <= hf->maxB)))
+        return fail(RVLM_ERR_ARG, who + (hf ? ": need 1 < B <= max_batch of both handles" : ": need 1 < B <= max_batch"));
+    if (!(iterations >= 0 && iterations <= 4096 && n_first >= 0)) return fail(RVLM_ERR_ARG, who + ": iterations");
+    return RVLM_OK;
 }
 
 extern "C" int rvlm_pgd_run_norm(rvlm_vit* h, const float* x, const float* delta0, int B,
@@ -1517,9 +1513,7 @@ extern "C" int rvlm_pgd_run_norm(rvlm_vit* h, const float* x, const float* delta
                                  float momentum, int mode_max, float* x_adv_out, float* loss_trace,
                                  int32_t* flags, rvlm_stream_t stream) {
     RVLM_REQUIRE(h && x && loss && x_adv_out && loss->ref, "rvlm_pgd_run: null argument");
-    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_pgd_run: norm must be L-inf (0) or L2 (2)");
-    RVLM_REQUIRE(B > 1 && B <= h->maxB, "rvlm_pgd_run: need 1 < B <= max_batch");
-    RVLM_REQUIRE(iterations >= 0 && iterations <= 4096, "rvlm_pgd_run: iterations");
+    int rc = pgd_loop_check("rvlm_pgd_run", norm_kind, iterations, 0, B, h); if (rc) return rc;
     return pgd_run_impl(h, PooledStep{h, nullptr, 0, loss, false}, x, delta0, B, norm_kind, eps, iterations, stepsize, momentum,
                         mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
 }
@@ -1535,9 +1529,7 @@ extern "C" int rvlm_pgd_run_mixed(rvlm_vit* h, rvlm_vit* h_first, int n_first, c
                                   float momentum, int mode_max, float* x_adv_out, float* loss_trace,
                                   int32_t* flags, rvlm_stream_t stream) {
     RVLM_REQUIRE(h && h_first && x && loss && x_adv_out && loss->ref, "rvlm_pgd_run_mixed: null argument");
-    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_pgd_run_mixed: norm must be L-inf (0) or L2 (2)");
-    RVLM_REQUIRE(B > 1 && B <= h->maxB && B <= h_first->maxB, "rvlm_pgd_run_mixed: need 1 < B <= max_batch of both handles");
-    RVLM_REQUIRE(iterations >= 0 && iterations <= 4096 && n_first >= 0, "rvlm_pgd_run_mixed: iterations");
+    int rc = pgd_loop_check("rvlm_pgd_run_mixed", norm_kind, iterations, n_first, B, h, h_first); if (rc) return rc;
     RVLM_REQUIRE(h->img == h_first->img && h->P == h_first->P && h->W == h_first->W && h->L == h_first->L &&
                  h->H == h_first->H && h->D == h_first->D && h->cfg.act == h_first->cfg.act,
                  "rvlm_pgd_run_mixed: the two handles must hold the same architecture");
@@ -1555,9 +1547,7 @@ extern "C" int rvlm_pgd_run_mixed_fwd(rvlm_vit* h, rvlm_vit* h_first, int n_firs
                                       float momentum, int mode_max, float* x_adv_out, float* loss_trace,
                                       int32_t* flags, rvlm_stream_t stream) {
     RVLM_REQUIRE(h && h_first && x && loss && x_adv_out && loss->ref, "rvlm_pgd_run_mixed_fwd: null argument");
-    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_pgd_run_mixed_fwd: norm must be L-inf (0) or L2 (2)");
-    RVLM_REQUIRE(B > 1 && B <= h->maxB && B <= h_first->maxB, "rvlm_pgd_run_mixed_fwd: need 1 < B <= max_batch of both handles");
-    RVLM_REQUIRE(iterations >= 0 && iterations <= 4096 && n_first >= 0, "rvlm_pgd_run_mixed_fwd: iterations");
+    int rc = pgd_loop_check("rvlm_pgd_run_mixed_fwd", norm_kind, iterations, n_first, B, h, h_first); if (rc) return rc;
     RVLM_REQUIRE(h->bf16 && !h_first->bf16, "rvlm_pgd_run_mixed_fwd: h must be a bf16 handle, h_first an fp32-storage (fp32 / x3) one");
     RVLM_REQUIRE(h->Mp == h_first->Mp && h->Mp0 == h_first->Mp0, "rvlm_pgd_run_mixed_fwd: the two handles need the same max_batch");
     RVLM_REQUIRE(!h->inference_only && !h_first->inference_only, "rvlm_pgd_run_mixed_fwd: inference-only handle");
@@ -1591,10 +1581,7 @@ extern "C" int rvlm_vit_backward_input_tokens(rvlm_vit* h, const float* d_tokens
     RVLM_REQUIRE(h && d_tokens && grad_x, "rvlm_vit_backward_input_tokens: null argument");
     if (h->provider || h->inference_only)
         return fail(RVLM_ERR_STATE, "rvlm_vit_backward_input_tokens: forward-provider and inference-only handles have no backward");
-    if (B <= 0 || h->saved_B != B || h->saved_mode != 4)
-        return fail(RVLM_ERR_STATE, h->saved_B > 0 && h->saved_mode != 4
-                        ? "rvlm_vit_backward_input_tokens: the saved forward is a pooled pass (rvlm_vit_backward_input differentiates it)"
-                        : "rvlm_vit_backward_input_tokens: no saved token forward for this batch size");
+    int rc = saved_check(h, Reader::Tokens, B); if (rc) return rc;
     RVLM_REQUIRE(!d_emb || h->saved_depth == h->L, "rvlm_vit_backward_input_tokens: d_emb needs a token pass of depth == layers");
     return vit_backward_tokens(h, TokSeed{d_tokens, h->saved_depth, h->saved_lnpost}, d_emb, B, grad_x, (hipStream_t)stream);
 }
@@ -1655,9 +1642,8 @@ extern "C" int rvlm_pgd_run_tokens(rvlm_vit* h, const float* x, const float* del
                                    float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags,
                                    rvlm_stream_t stream) {
     RVLM_REQUIRE(h && x && x_adv_out, "rvlm_pgd_run_tokens: null argument");
-    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_pgd_run_tokens: norm must be L-inf (0) or L2 (2)");
-    RVLM_REQUIRE(iterations >= 0 && iterations <= 4096, "rvlm_pgd_run_tokens: iterations");
-    int rc = tokens_loop_check(h, B, depth, select, ref_tokens, reduction, "rvlm_pgd_run_tokens"); if (rc) return rc;
+    int rc = pgd_loop_check("rvlm_pgd_run_tokens", norm_kind, iterations, 0, B, nullptr); if (rc) return rc;      // (batch: tokens_loop_check)
+    rc = tokens_loop_check(h, B, depth, select, ref_tokens, reduction, "rvlm_pgd_run_tokens"); if (rc) return rc;
     if (ln_post && (rc = tok_ensure(h, true))) return rc;
     return pgd_run_impl(h, TokenStep{h, depth, ln_post != 0, select, ref_tokens, reduction, flags}, x, delta0, B, norm_kind, eps,
                         iterations, stepsize, momentum, mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
