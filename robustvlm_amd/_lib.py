@@ -283,7 +283,7 @@ _SIGS.update({
                                             C.POINTER(C.c_float), c_f32p, c_stream]),
 })
 _SIGS.update({
-    # token-level outputs and their input gradient (csrc/token_kernels.hip, csrc/engine.hip; RVLM_HAS_TOKENS)
+    # token-level outputs and their input gradient (csrc/token_kernels.hip, csrc/engine_forward.hip / engine_backward.hip / engine_attacks.hip; RVLM_HAS_TOKENS)
     "rvlm_vit_forward_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_stream]),
     "rvlm_vit_backward_input_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, c_f32p, c_stream]),
     "rvlm_tokens_l2_loss_grad": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, C.c_long,

@@ -19,6 +19,8 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 // ---- error plumbing (no exceptions across the ABI) --------------------------------------------
 void set_error(const std::string& msg);
 int fail(int code, const std::string& msg);
+// an integer switch of the environment (atoi of its value), dflt where it is unset
+int env_int(const char* name, int dflt);
 
 #define RVLM_HIP(expr)                                                                       \
     do {                                                                                     \

@@ -156,7 +156,7 @@ int l2_normalize_bwd(const float* d_out, const float* e_raw, const float* inv_no
 // ---------------------------------------------------------------------------------------------
 // rows of `cols` values, `ld` floats apart.  lse2 != null: the rows are the [cols x cols] score matrices of (image, head) pairs and
 // lse2[(row / cols) * lse_ld + row % cols] = log2(sum_j exp(s_j)) - the bf16 flash kernels' log-sum-exp convention (attention_bf16.hip),
-// so that their backward can run on a forward this path computed (the handoff of engine.hip)
+// so that their backward can run on a forward this path computed (the handoff, engine_backward.hip)
 int softmax_rows_fwd(float* s, long rows, int cols, int ld, hipStream_t st, float* lse2 = nullptr, int lse_ld = 0);
 // ds = p * (dp - sum_j p_j dp_j) * scale, in place over dp
 int softmax_rows_bwd(const float* p, float* dp, long rows, int cols, int ld, float scale, hipStream_t st);

@@ -379,7 +379,7 @@ extern "C" int rvlm_k_wgrad_bf16(const uint16_t* dY, long lddy, const uint16_t* 
         if (!rc) rc = gemm_bf16_wgrad_split(tA, tB, splits, Kc, N, K, dW, lddw, accumulate, slab, slab_bytes, (hipStream_t)stream);
         return rc;
     }
-    // the training step's path (engine.hip wgrad<bf16_t>): column sums + the contraction-major persistent GEMM on the operands as they lie
+    // the training step's path (engine_backward.hip wgrad<bf16_t>): column sums + the contraction-major persistent GEMM on the operands as they lie
     if (!rc && dbias) rc = colsum<bf16_t>((const bf16_t*)dY, lddy, M, N, dbias, accumulate, red, redf, (hipStream_t)stream);
     if (!rc) rc = gemm_bf16_wgrad_tn((const bf16_t*)dY, lddy, (const bf16_t*)X, ldx, M, splits, Kc, N, K, dW, lddw, accumulate, slab,
                                      slab_bytes, (hipStream_t)stream);

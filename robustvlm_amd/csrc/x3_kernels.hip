@@ -146,7 +146,7 @@ int x3_act(const float* hbuf, long ldh, float* out, long ldo, bf16_t* A3, int M,
 }
 
 // ---- handoff to the bf16 engine (round 6): the forward ran here (fp32 storage), the input gradient runs on the bf16 handle's
-// kernels (engine.hip, vit_backward_from) - FARE's first-iteration noise sits in the forward DIFFERENCE phi(x + d0) - phi(x), not in
+// kernels (engine_backward.hip, vit_backward_from) - FARE's first-iteration noise sits in the forward DIFFERENCE phi(x + d0) - phi(x), not in
 // the cotangent's way back (oracle/split_bf16_emulation.py, arm x3fwd-bf16bwd-flash: gradient-sign agreement with the fp32 oracle
 // 0.998 against 0.9996 for a split-bf16 backward and 0.82 for the bf16 forward).  What the bf16 backward reads in bf16 - qkv, the
 // attention output, act'(h) - is exported from the fp32 tensors the forward kept; 8 columns per lane, 16-byte stores.

@@ -770,7 +770,7 @@ def test_x3_falls_back_to_the_fp32_tiles_on_small_shapes():
         R.VitEngine(to_cfg(cfg), {k: v.to(dev()) for k, v in w.items()}, precision="x3", max_batch=4, trainable=True)
 
 
-# ---- handoff: fp32-storage forward, bf16 backward (round 6; engine.hip::vit_backward_from) ---------------------------------
+# ---- handoff: fp32-storage forward, bf16 backward (round 6; engine_backward.hip::vit_backward_from) ---------------------------------
 @pytest.mark.parametrize("shape", ["s65", "s257", "s577", "tiny"])
 @pytest.mark.parametrize("normalize", [False, True])
 def test_handoff_backward_from_x3_forward(shape, normalize):

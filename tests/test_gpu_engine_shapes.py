@@ -66,7 +66,7 @@ def test_engine_shape_sweep(W, img, P, clip_like):
         tag = f"W {W} S {S} B {B}"
         e32, ex3, e16, eho = (err[p][i] for p in ("fp32", "x3", "bf16", "bf16+x3fwd-first"))
         assert e32[0] < 1e-4 and e32[1] < 1e-3, (tag, e32)
-        takes = W % 256 == 0 and B * S >= 256                 # engine.hip x3_takes for every encoder linear of these shapes
+        takes = W % 256 == 0 and B * S >= 256                 # linear.h x3_takes for every encoder linear of these shapes
         if takes:
             assert ex3[0] < 5e-5 and ex3[1] < 2e-4, (tag, ex3)
             assert ex3[0] < 0.05 * e16[0] and ex3[1] < 0.05 * e16[1], (tag, ex3, e16)

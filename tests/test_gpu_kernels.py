@@ -476,7 +476,7 @@ def test_gemm_bf16_act_epilogue_without_derivative_output(M, N, K, variant, fam,
 
 
 # the eight GEMM launch types of one ViT-L/14 block at the headline batch (B = 128: M = 128 * 257 = 32 896 rows), as
-# (name, N, K, epilogue): forward QKV / out-proj / fc1 / fc2 and their dgrads (robustvlm_amd/csrc/engine.hip)
+# (name, N, K, epilogue): forward QKV / out-proj / fc1 / fc2 and their dgrads (robustvlm_amd/csrc/engine_forward.hip, engine_backward.hip)
 HEADLINE_GEMMS = [("qkv_fwd", 3072, 1024, 0), ("out_fwd", 1024, 1024, 1), ("fc1_fwd", 4096, 1024, 2),
                   ("fc2_fwd", 1024, 4096, 1), ("fc2_bwd", 4096, 1024, 3), ("fc1_bwd", 1024, 4096, 0),
                   ("qkv_bwd", 1024, 3072, 0), ("out_bwd", 1024, 1024, 0)]
