@@ -13,7 +13,9 @@ the max-over-ranks time.
 torch.distributed.run on 127.0.0.1, exit code of the ranks); started under one (WORLD_SIZE set) it is a rank, and --gpus has
 to equal WORLD_SIZE.  More GPUs than the node shows is an error, never a silently smaller job.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run does what that line's headline figure needs and nothing else: it sets up, warms up,
+times the --steps calls, writes --dump-outputs and prints.  --full adds, from untimed calls and child runs AFTER the timed steps
+(the timed region and the headline keys are the same either way), two objects and the per-rank clocks:
   roofline     - bf16 MFMA GEMM kernel: algorithmic FLOPs / HIP-event launch time, vs 2.5 PFLOP/s; the shader clock held
                  during the timed region (rocm-smi) and inside the GEMM launches (the kernel's own cycle / real-time stamps),
                  the fraction against the peak at that clock, per-class times, the committed in-pipeline PMC summary
@@ -66,10 +68,15 @@ def parse(extra=None):
     ap.add_argument("--always-reduce", action="store_true",
                     help="train mode on ONE GPU: run the bucketed RCCL all-reduce path in a one-rank group (identity reduction) "
                          "so that its launch / wait structure and the `allreduce` diagnostics can be exercised without a node")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the shader clock / socket power "
+                         "of every rank over extra calls, the `roofline` object (a profiled call, rocprofv3 --pmc child runs), the "
+                         "`cpu_baseline` object (the oracle on this host's cores), train mode's `allreduce` diagnostics.  Off by "
+                         "default: a plain run ends with the timed steps, and the three --no-* options below have nothing to skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave `roofline` and the per-rank clocks out")
     ap.add_argument("--no-pmc", action="store_true",
-                    help="skip the in-run rocprofv3 --pmc passes (fabric traffic, matrix-pipe busy): roofline.traffic / "
+                    help="with --full: skip the in-run rocprofv3 --pmc passes (fabric traffic, matrix-pipe busy): roofline.traffic / "
                          "pmc_in_pipeline then come from the committed profiles/ files, flagged measured_in_run: false")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, rank 0 writes what the LAST timed step returned to its caller as DIR/<name>.npy "
@@ -81,6 +88,8 @@ def parse(extra=None):
     args = ap.parse_args()
     if not hasattr(args, "norm"):
         args.norm = "linf"
+    if not args.full:               # a plain run: after the timed steps only --dump-outputs and the line
+        args.no_cpu_baseline = args.no_roofline = args.no_pmc = True
     return args
 
 
@@ -198,8 +207,8 @@ def bench_train(args, R, cfg, sd, dev, dist, world, rank, coll_dev=None, rehears
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
     barrier()
-    # with more than one rank (or --always-reduce on one): per-bucket all-reduce times and how much of them the backward hid
-    ar = tr.profile_allreduce(x) if tr._reduce else None
+    # --full with more than one rank (or --always-reduce on one): per-bucket all-reduce times and how much of them the backward hid
+    ar = tr.profile_allreduce(x) if args.full and tr._reduce else None
     if rank == 0:
         print(json.dumps({
             "allreduce": ar, **({"rehearsal": REHEARSAL_NOTE} if rehearsal else {}),
@@ -444,8 +453,7 @@ def main(extra=None):
         if headline and world == 1 and not args.no_pmc and not os.environ.get("RVLM_BENCH_CHILD"):
             try:
                 torch.cuda.synchronize()
-                traffic, traffic_src, pmc = pmc_in_run(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-roofline", "--no-pmc",
-                                                        "--iterations", str(args.iterations)])
+                traffic, traffic_src, pmc = pmc_in_run(["--steps", "1", "--warmup", "0", "--iterations", str(args.iterations)])
             except Exception as e:                    # measurement aid: fall back to the committed passes, flagged as such
                 pmc_error = f"{type(e).__name__}: {e}"[:400]
                 traffic, traffic_src, pmc = None, None, None

@@ -84,8 +84,8 @@ def hbm_classes(prof: dict, cfg, B: int, traffic: dict | None = None) -> dict:
 def pmc_in_run(argv_child, timeout_s=240):
     """`roofline.traffic` and the in-pipeline matrix-pipe figures measured IN THIS RUN, on this box and build: PMC counters cannot
     be read from inside the process, so rank 0 runs this same script under `rocprofv3 --pmc` as a child (one counter group per
-    pass, --kernel-trace only - no sys/hip/hsa trace domains next to --pmc; the child times one pgd() call + the e0 forward,
-    --no-roofline --no-cpu-baseline --no-pmc) while the parent's stream is idle, and sums the counters per kernel like
+    pass, --kernel-trace only - no sys/hip/hsa trace domains next to --pmc; the child is a plain run: one pgd() call + the e0
+    forward) while the parent's stream is idle, and sums the counters per kernel like
     scripts/pmc_traffic.sh / pmc_pipeline.sh.  FETCH_SIZE is DOUBLED (MI355X_MICROARCH.md, HBM section: gfx950 reports half the
     bytes of wide coalesced reads), both counters are KiB.  Returns (traffic_bytes_per_gemm_launch, info, pmc) or raises."""
     import collections

@@ -10,6 +10,7 @@ nproc >> gpurun_out/device.txt
 echo "smoke rc=$?" >> gpurun_out/smoke.log
 ( timeout 1800 python -m pytest tests -m gpu -q -n 1 -p no:cacheprovider ${PYTEST_ARGS:-} ) > gpurun_out/pytest_gpu.log 2>&1
 echo "pytest rc=$?" >> gpurun_out/pytest_gpu.log
+BENCH_ARGS="--full ${BENCH_ARGS:-}"      # the bench line with its roofline and cpu_baseline objects
 if [ "${SKIP_BENCH:-0}" != "1" ]; then
   ( timeout 900 python bench.py --steps 3 --warmup 1 ${BENCH_ARGS:-} ) > gpurun_out/bench.log 2>&1
   echo "bench rc=$?" >> gpurun_out/bench.log

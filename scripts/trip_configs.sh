@@ -2,7 +2,8 @@
 # bench lines of the other BASELINE configurations and the training step (builder-run; the driver measures config 2)
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-run() { tag=$1; shift; ( timeout 900 python ${BENCH_SCRIPT:-bench.py} --no-cpu-baseline "$@" ) > gpurun_out/bench_$tag.log 2>&1; echo "$tag rc=$?"; tail -c 420 gpurun_out/bench_$tag.log | head -c 300; echo; }
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # where the bench lines go
+run() { tag=$1; shift; ( timeout 900 python ${BENCH_SCRIPT:-bench.py} --full --no-cpu-baseline "$@" ) > $OUT/bench_$tag.log 2>&1; echo "$tag rc=$?"; tail -c 420 $OUT/bench_$tag.log | head -c 300; echo; }
 run c3 --attack apgd --steps 3 --warmup 1
 run c5 --attack autopgd --iterations 100 --batch 256 --steps 1 --warmup 1 --no-roofline
 run train --mode train --steps 3 --warmup 1

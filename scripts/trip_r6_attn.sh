@@ -3,6 +3,7 @@
 # phase split, in-pipeline A/B, then the full-size suite (CLIP-like fixture included).
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out; export TMPDIR=/tmp
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # where the bench lines go
 for pf in 1 0; do
   ( export RVLM_ATTN_BWD_PF=$pf; timeout 900 python -m pytest tests/test_gpu_kernels.py tests/test_gpu_engine.py -m gpu -q -x -p no:cacheprovider -k "attention or attn or engine_vs_oracle" ) 2>&1 | tail -3 | tee -a gpurun_out/attn_pf_tests.log
 done
@@ -14,14 +15,14 @@ for pf in 0 1; do
 done
 grep -E "bwd|==" gpurun_out/attn_ab_pf.log | cut -c1-150
 for rep in 1 2; do for pf in 0 1; do
-  ( export RVLM_ATTN_BWD_PF=$pf; timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-pmc ) > gpurun_out/bench_pf${pf}_$rep.log 2>&1
+  ( export RVLM_ATTN_BWD_PF=$pf; timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-pmc ) > $OUT/bench_pf${pf}_$rep.log 2>&1
   python - <<PY
 import json
-for l in open("gpurun_out/bench_pf${pf}_$rep.log"):
+for l in open("$OUT/bench_pf${pf}_$rep.log"):
     if l.startswith("{"):
         d = json.loads(l); pc = d["roofline"]["per_class"]
         print("PF=$pf rep $rep: %.1f img/s, attn_bwd %.2f ms, attn_fwd %.2f ms, clock %.0f" % (d["value"], pc["attn_bwd"]["ms"], pc["attn_fwd"]["ms"], d["roofline"]["clock_in_kernel"]["sclk_mhz_effective"]))
 PY
-done; done 2>&1 | tee gpurun_out/bench_pf_ab.log
+done; done 2>&1 | tee $OUT/bench_pf_ab.log
 rm -f gpurun_out/parity_metrics.jsonl
 ( timeout 1500 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -p no:cacheprovider --durations=5 ) > gpurun_out/pytest_fullsize.log 2>&1; tail -15 gpurun_out/pytest_fullsize.log

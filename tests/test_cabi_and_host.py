@@ -197,6 +197,23 @@ def test_bench_host_helpers():
     assert b.bind_rank_to_numa(0, 1) is None
 
 
+def test_bench_full_option(monkeypatch):
+    """bench.py --full: off by default, and without it nothing but the timed steps is asked for; the --no-* options refine --full."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+
+    def extras(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        a = b.parse()
+        return a.full, not a.no_roofline, not a.no_pmc, not a.no_cpu_baseline
+    assert extras("--gpus", "1", "--steps", "20", "--warmup", "5") == (False, False, False, False)
+    assert extras("--no-pmc") == (False, False, False, False)
+    assert extras("--full") == (True, True, True, True)
+    assert extras("--full", "--no-cpu-baseline", "--no-pmc") == (True, True, False, False)
+
+
 def test_bench_dump_outputs(tmp_path):
     """bench.py --dump-outputs: one .npy per returned value, float32 / float64 only, a fixed sample once the budget is exceeded."""
     import importlib.util

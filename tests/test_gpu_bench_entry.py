@@ -38,7 +38,7 @@ def test_world_size_mismatch_exits_nonzero():
 
 def test_single_gpu_line(tmp_path):
     """N = 1 prints ONE JSON line with the contract's keys (small model so that the test stays short)."""
-    r = run("--gpus", "1", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "8", "--no-cpu-baseline")
+    r = run("--gpus", "1", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "8", "--full", "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -47,6 +47,20 @@ def test_single_gpu_line(tmp_path):
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
     assert d["n_gpus"] == 1 and d["ranks"]["rccl_ranks"] == 0 and d["value"] > 0
+
+
+def test_plain_run_ends_with_the_timed_steps():
+    """Without --full the line carries the headline keys and nothing that takes calls or child runs of its own: no `roofline`, no
+    `cpu_baseline`, no clock readings - and the --no-* options, which refine --full, change nothing."""
+    for more in ((), ("--no-cpu-baseline", "--no-roofline", "--no-pmc")):
+        d = _one_line(run("--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "ViT-B-32", "--batch", "8", *more))
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                  "vs_baseline", "dtype", "data", "config", "ranks"):
+            assert k in d, k
+        assert "roofline" not in d and "cpu_baseline" not in d
+        assert d["steps"] == 2 and d["value"] > 0 and abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        (r,) = d["ranks"]["per_rank"]
+        assert r["sclk_in_kernel_mhz"] is None and r["sclk_smi_mhz_mean"] is None and r["socket_power_w_mean"] is None
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs")
@@ -74,7 +88,7 @@ def _one_line(r):
 
 
 def test_two_rank_rehearsal_attack_line():
-    d = _one_line(run("--gpus", "2", *SMALL, env=REH))
+    d = _one_line(run("--gpus", "2", *SMALL, "--full", env=REH))
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert "rehearsal" in d and "REHEARSAL" in d["data"]
     rk = d["ranks"]
@@ -117,7 +131,7 @@ def test_two_rank_rehearsal_dying_rank_exits_nonzero():
 def test_two_rank_rehearsal_train_step_line():
     """--mode train --gpus 2: the bucketed gradient all-reduce (through the host copy, gloo) inside bench.py's own loop."""
     d = _one_line(run("--gpus", "2", "--mode", "train", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "4",
-                      "--iterations", "2", env=REH, timeout=900))
+                      "--iterations", "2", "--full", env=REH, timeout=900))
     assert d["n_gpus"] == 2 and "rehearsal" in d and d["value"] > 0
     assert d["allreduce"]["world"] == 2 and "gloo" in d["allreduce"]["backend"]
     assert d["final_loss"] == d["final_loss"]        # finite
@@ -153,14 +167,14 @@ def test_dump_outputs_train_step(tmp_path):
 def test_fp32_line_is_priced_against_the_fp32_matrix_peak():
     """--precision fp32 (the reference's own precision on v_mfma_f32_32x32x2_f32): dtype, roofline peak and kernel name of the line."""
     d = _one_line(run("--gpus", "1", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "8", "--precision", "fp32",
-                      "--no-cpu-baseline"))
+                      "--full", "--no-cpu-baseline"))
     assert d["dtype"] == "fp32" and d["roofline"]["peak"] == 157.3 and "gemm_f32_mfma_kernel" in d["roofline"]["kernel"]
     assert 0 < d["roofline"]["frac"] < 1
 
 
 def test_mixed_precision_line():
     d = _one_line(run("--gpus", "1", "--steps", "1", "--warmup", "1", "--model", "ViT-B-32", "--batch", "8", "--precision",
-                      "bf16+fp32-first", "--no-cpu-baseline"))
+                      "bf16+fp32-first", "--full", "--no-cpu-baseline"))
     assert d["dtype"] == "bf16+fp32-first" and d["value"] > 0 and d["roofline"]["peak"] == 2500.0
 
 
