@@ -178,6 +178,34 @@ int rvlm_k_l2_normalize_bwd(const float* d_out, const float* e_raw, const float*
  * dlp (bf16) rows [0, M) = d_tok (+ cls_add[b, :] on row b S, cls_add [B, W] or NULL), rows [M, Mp) = 0.  W % 8 == 0. */
 int rvlm_k_tokens_seed(const float* d_tok, const float* cls_add, float* d32, uint16_t* dlp, int M, int Mp, int S, int W,
                        rvlm_stream_t stream);
+
+/* The training step's kernels, one entry per host launcher of csrc/train_kernels.hip (tests/test_gpu_train_kernels.py).  Leading
+ * dimensions in elements.  The column reductions run in two passes - R rows in rvlm_k_reduce_chunks(R) row chunks, then the sum of the
+ * chunks' partials - and take caller-owned scratch `red` of red_floats floats: rvlm_k_reduce_chunks(R) * C for rvlm_k_colsum, twice
+ * that for rvlm_k_ln_param_grad; RVLM_ERR_STATE (nothing launched) when it is smaller.  rvlm_k_colsum_form: the form rvlm_k_colsum
+ * runs for an operand of that element type, width, leading dimension and address (only the address's low four bits matter) - the
+ * dispatchers' own rules, like rvlm_k_layernorm_form. */
+#define RVLM_COLSUM_FORM_GENERIC 0   /* colsum_partial_kernel<T>: 64 columns x 4 row lanes per workgroup, one element per lane */
+#define RVLM_COLSUM_FORM_16B 1       /* colsum8_partial_kernel: bf16, C % 256 == 0, every row 16-byte aligned; 16 B per lane */
+int rvlm_k_reduce_chunks(int R);
+int rvlm_k_colsum_form(int bf16_in, int C, long ld, size_t base_alignment);
+/* out[c] (+)= sum_r in[r, c]; in [R, C] fp32, or bf16 with bf16_in (bias gradients) */
+int rvlm_k_colsum(const void* in, int bf16_in, long ld, int R, int C, float* out, int accumulate, float* red, size_t red_floats,
+                  rvlm_stream_t stream);
+/* LayerNorm affine gradients: dgamma[c] (+)= sum_r dy[r, c] (x[r, c] - mean[r]) rstd[r], dbeta[c] (+)= sum_r dy[r, c]; dy fp32, or
+ * bf16 with bf16_dy; x fp32; mean / rstd [R] */
+int rvlm_k_ln_param_grad(const void* dy, int bf16_dy, long lddy, const float* x, long ldx, const float* mean, const float* rstd,
+                         int R, int C, float* dgamma, float* dbeta, int accumulate, float* red, size_t red_floats,
+                         rvlm_stream_t stream);
+/* dpos[s, c] (+)= sum_b dtok[b S + s, c] (dpos [S, W] contiguous), dcls[c] (+)= the same for s = 0 */
+int rvlm_k_pos_cls_grad(const float* dtok, long ld, int B, int S, int W, float* dpos, float* dcls, int accumulate,
+                        rvlm_stream_t stream);
+/* d_patch[b (S - 1) + s - 1, :] = dtok[b S + s, :] for s >= 1 (the class rows are not read); d_patch fp32, or bf16 (round to nearest
+ * even) with bf16_out */
+int rvlm_k_gather_patch_rows(const float* dtok, long ld, int B, int S, int W, void* d_patch, long ldp, int bf16_out,
+                             rvlm_stream_t stream);
+/* bf16: out[c, r] = in[r, c] for r < R, 0 for R <= r < Rp (the K padding of the weight-gradient GEMM); out [C, Rp], rows ldo apart */
+int rvlm_k_transpose_pad(const uint16_t* in, long ldi, int R, int C, uint16_t* out, long ldo, int Rp, rvlm_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

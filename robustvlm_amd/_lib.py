@@ -294,6 +294,17 @@ _SIGS.update({
                                       C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, c_f32p, c_f32p, C.c_void_p, c_stream]),
     "rvlm_k_tokens_seed": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
 })
+_SIGS.update({
+    # the training step's kernels (csrc/train_kernels.hip; include/rvlm_kernels.h, tests/test_gpu_train_kernels.py)
+    "rvlm_k_reduce_chunks": (C.c_int, [C.c_int]),
+    "rvlm_k_colsum_form": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_size_t]),
+    "rvlm_k_colsum": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, C.c_size_t, c_stream]),
+    "rvlm_k_ln_param_grad": (C.c_int, [C.c_void_p, C.c_int, C.c_long, c_f32p, C.c_long, c_f32p, c_f32p, C.c_int, C.c_int, c_f32p,
+                                       c_f32p, C.c_int, c_f32p, C.c_size_t, c_stream]),
+    "rvlm_k_pos_cls_grad": (C.c_int, [c_f32p, C.c_long, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_stream]),
+    "rvlm_k_gather_patch_rows": (C.c_int, [c_f32p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, c_stream]),
+    "rvlm_k_transpose_pad": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

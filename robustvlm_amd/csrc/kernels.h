@@ -228,7 +228,10 @@ int gemm_bf16_wgrad_tn(const bf16_t* dY, long lddy, const bf16_t* X, long ldx, i
                        long lddw, int accumulate, float* slab, size_t slab_bytes, hipStream_t s);
 int gemm_bf16_wgrad_split(const bf16_t* tA, const bf16_t* tB, int splits, int Kc, int N, int K, float* dW, long lddw,
                           int accumulate, float* slab, size_t slab_bytes, hipStream_t s);
-// `red` / `red_floats`: caller-owned scratch for the partial column sums (no process-wide state)
+// `red` / `red_floats`: caller-owned scratch for the partial column sums (no process-wide state): reduce_chunks(R) * C floats for
+// colsum, twice that for ln_param_grad.  colsum8_covers: colsum runs its 16-byte bf16 form (`base` = the operand's address).
+int reduce_chunks(int R);
+bool colsum8_covers(bool bf16_in, int C, long ld, size_t base);
 template <typename T>
 int colsum(const T* in, long ld, int R, int C, float* out, int accumulate, float* red, size_t red_floats,
            hipStream_t s);

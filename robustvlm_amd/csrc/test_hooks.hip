@@ -476,3 +476,42 @@ extern "C" int rvlm_k_tokens_seed(const float* d_tok, const float* cls_add, floa
                                   rvlm_stream_t stream) {
     return tokens_seed(d_tok, cls_add, W, d32, (bf16_t*)dlp, M, Mp, S, W, (hipStream_t)stream);
 }
+
+// ---- the training step's kernels, one hook per host launcher of train_kernels.hip (tests/test_gpu_train_kernels.py) ----
+extern "C" int rvlm_k_reduce_chunks(int R) { return reduce_chunks(R); }
+extern "C" int rvlm_k_colsum_form(int bf16_in, int C, long ld, size_t base_alignment) {
+    return colsum8_covers(bf16_in != 0, C, ld, base_alignment) ? RVLM_COLSUM_FORM_16B : RVLM_COLSUM_FORM_GENERIC;
+}
+extern "C" int rvlm_k_colsum(const void* in, int bf16_in, long ld, int R, int C, float* out, int accumulate, float* red,
+                             size_t red_floats, rvlm_stream_t stream) {
+    if (!in || !out || R <= 0 || C <= 0 || ld < C) return fail(RVLM_ERR_ARG, "rvlm_k_colsum: bad arguments");
+    if (bf16_in) return colsum<bf16_t>((const bf16_t*)in, ld, R, C, out, accumulate, red, red_floats, (hipStream_t)stream);
+    return colsum<float>((const float*)in, ld, R, C, out, accumulate, red, red_floats, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_ln_param_grad(const void* dy, int bf16_dy, long lddy, const float* x, long ldx, const float* mean,
+                                    const float* rstd, int R, int C, float* dgamma, float* dbeta, int accumulate, float* red,
+                                    size_t red_floats, rvlm_stream_t stream) {
+    if (!dy || !x || !mean || !rstd || !dgamma || !dbeta || R <= 0 || C <= 0 || lddy < C || ldx < C)
+        return fail(RVLM_ERR_ARG, "rvlm_k_ln_param_grad: bad arguments");
+    if (bf16_dy)
+        return ln_param_grad<bf16_t>((const bf16_t*)dy, lddy, x, ldx, mean, rstd, R, C, dgamma, dbeta, accumulate, red, red_floats,
+                                     (hipStream_t)stream);
+    return ln_param_grad<float>((const float*)dy, lddy, x, ldx, mean, rstd, R, C, dgamma, dbeta, accumulate, red, red_floats,
+                                (hipStream_t)stream);
+}
+extern "C" int rvlm_k_pos_cls_grad(const float* dtok, long ld, int B, int S, int W, float* dpos, float* dcls, int accumulate,
+                                   rvlm_stream_t stream) {
+    if (!dtok || !dpos || !dcls || B <= 0 || S <= 0 || W <= 0 || ld < W) return fail(RVLM_ERR_ARG, "rvlm_k_pos_cls_grad: bad arguments");
+    return pos_cls_grad(dtok, ld, B, S, W, dpos, dcls, accumulate, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_gather_patch_rows(const float* dtok, long ld, int B, int S, int W, void* d_patch, long ldp, int bf16_out,
+                                        rvlm_stream_t stream) {
+    if (!dtok || !d_patch || B <= 0 || S <= 1 || W <= 0 || ld < W || ldp < W)
+        return fail(RVLM_ERR_ARG, "rvlm_k_gather_patch_rows: bad arguments");
+    if (bf16_out) return gather_patch_rows<bf16_t>(dtok, ld, B, S, W, (bf16_t*)d_patch, ldp, (hipStream_t)stream);
+    return gather_patch_rows<float>(dtok, ld, B, S, W, (float*)d_patch, ldp, (hipStream_t)stream);
+}
+extern "C" int rvlm_k_transpose_pad(const uint16_t* in, long ldi, int R, int C, uint16_t* out, long ldo, int Rp, rvlm_stream_t stream) {
+    if (!in || !out || R <= 0 || C <= 0 || Rp < R || ldi < C || ldo < Rp) return fail(RVLM_ERR_ARG, "rvlm_k_transpose_pad: bad arguments");
+    return transpose_pad<bf16_t>((const bf16_t*)in, ldi, R, C, (bf16_t*)out, ldo, Rp, (hipStream_t)stream);
+}

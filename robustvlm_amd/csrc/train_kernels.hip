@@ -197,11 +197,19 @@ colsum8_partial_kernel(const bf16_t* __restrict__ in, long ld, int R, int C, flo
     partial[(long)blockIdx.y * C + blockIdx.x * 256 + t] =
         ((red[0][t] + red[1][t]) + (red[2][t] + red[3][t])) + ((red[4][t] + red[5][t]) + (red[6][t] + red[7][t]));
 }
+// The two host rules of the column reductions, each written once: the dispatchers below and the test hooks (rvlm_k_reduce_chunks,
+// rvlm_k_colsum_form) ask these.
+// Row chunks (grid.y of the partial kernels, partial rows of reduce_partials16_kernel) at R rows.
+int reduce_chunks(int R) { return R >= 4096 ? RED_NCH : (R >= 256 ? 16 : 1); }
+// colsum takes colsum8_partial_kernel (16 B per lane): bf16 rows of C % 256 == 0 columns whose every row starts 16-B aligned (`base`:
+// the operand's address - its low four bits decide).
+bool colsum8_covers(bool bf16_in, int C, long ld, size_t base) { return bf16_in && C % 256 == 0 && ld % 8 == 0 && (base & 15) == 0; }
+
 template <typename T>
 int colsum(const T* in, long ld, int R, int C, float* out, int accumulate, float* red, size_t red_floats, hipStream_t s) {
-    const int nch = R >= 4096 ? RED_NCH : (R >= 256 ? 16 : 1);
+    const int nch = reduce_chunks(R);
     if (!red || (size_t)nch * C > red_floats) return fail(RVLM_ERR_STATE, "colsum: no reduce scratch");
-    if (std::is_same<T, bf16_t>::value && C % 256 == 0 && ld % 8 == 0 && ((size_t)in & 15) == 0) {
+    if (colsum8_covers(std::is_same<T, bf16_t>::value, C, ld, (size_t)in)) {
         hipLaunchKernelGGL(colsum8_partial_kernel, dim3(C / 256, nch), dim3(256), 0, s, (const bf16_t*)in, ld, R, C, red);
         RVLM_CHECK_LAUNCH();
         hipLaunchKernelGGL(reduce_partials16_kernel, dim3(cdiv(C, 16)), dim3(256), 0, s, red, nch, C, out, accumulate);
@@ -221,7 +229,7 @@ template int colsum<bf16_t>(const bf16_t*, long, int, int, float*, int, float*, 
 template <typename T>
 int ln_param_grad(const T* dy, long lddy, const float* x, long ldx, const float* mean, const float* rstd, int R,
                   int C, float* dgamma, float* dbeta, int accumulate, float* red, size_t red_floats, hipStream_t s) {
-    const int nch = R >= 4096 ? RED_NCH : (R >= 256 ? 16 : 1);
+    const int nch = reduce_chunks(R);
     if (!red || (size_t)2 * nch * C > red_floats) return fail(RVLM_ERR_STATE, "ln_param_grad: no reduce scratch");
     float* pg = red;
     float* pb = red + (size_t)nch * C;

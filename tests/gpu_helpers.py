@@ -126,3 +126,24 @@ def assert_rows(name, got, ref, bar, dims=("b", "h", "row")):
     where = ", ".join(f"{n} {i}" for n, i in zip(dims[len(dims) - len(idx):], idx))
     assert worst <= bar, f"{name}: worst row ({where}) has relative L2 error {worst:.3e} > {bar:.1e}"
     return worst
+
+
+def elem_rel(got, ref, floor):
+    """Element-wise |got - ref| / max(|ref|, floor) in fp64.  ``floor`` (broadcast against ref) is the absolute scale of an element:
+    for a sum of R terms the L2 norm of its terms (sqrt(R) x their RMS), so that a sum that nearly cancels is judged against the size
+    of what was added up instead of against its own near-zero value."""
+    got, ref = got.double(), ref.double()
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    return (got - ref).abs() / torch.maximum(ref.abs(), floor.double().expand_as(ref)).clamp_min(1e-300)
+
+
+def assert_elems(name, got, ref, floor, bar, dims=("row", "col")):
+    """Every element of ``got`` within ``bar`` of ``ref`` (elem_rel); the message names the worst element.  Returns the worst value."""
+    e = elem_rel(got, ref, floor)
+    flat = int(torch.nan_to_num(e, nan=float("inf")).argmax())          # a NaN element is the worst element
+    idx = np.unravel_index(flat, tuple(e.shape))
+    worst = float(e.flatten()[flat])
+    where = ", ".join(f"{n} {i}" for n, i in zip(dims[len(dims) - len(idx):], idx))
+    assert worst <= bar, (f"{name}: worst element ({where}) is {float(got.flatten()[flat])!r}, reference {float(ref.flatten()[flat])!r}: "
+                          f"error {worst:.3e} of its scale > {bar:.1e}")
+    return worst

@@ -506,3 +506,159 @@ def test_train_step_vs_reference_train_one_epoch(name):
                     got = torch.cat([got[:W], got[2 * W:]]); want = torch.cat([want[:W], want[2 * W:]])
                 assert rel_max(got, want) < 2e-2, (s, k, rel_max(got, want))
     tr.close()
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The parameter pass where a real batch puts it.  The column reductions behind every bias / LayerNorm gradient run in 1, 16 or
+# 128 row chunks by row count (csrc/train_kernels.hip reduce_chunks: 256 and 4 096 rows are the boundaries); the tests above stay
+# below 1 100 rows, a training step at B = 128 has 32 896.  tests/test_gpu_train_kernels.py holds the kernels themselves.
+# --------------------------------------------------------------------------------------------------------------------
+def reduction_produced(k):
+    """Parameter gradients that come out of the reduction kernels (colsum, ln_param_grad, pos_cls_grad), not of a GEMM."""
+    return k.endswith("bias") or "ln_" in k or k in ("positional_embedding", "class_embedding")
+
+
+def tensor_rel_l2(got, ref):
+    got, ref = got.double(), ref.double()
+    return float((got - ref).norm() / ref.norm())
+
+
+def record_by_kind(tag, rows):
+    """rows of (key, relative L2, worst element) -> one record and one printed line per kind of tensor (a block tensor: the worst of
+    the blocks)."""
+    from tests.gpu_helpers import record
+    kinds = {}
+    for k, l2, e in rows:
+        kind = k.split(".", 3)[-1] if k.startswith("transformer.resblocks.") else k
+        o = kinds.get(kind, (0.0, 0.0))
+        kinds[kind] = (max(o[0], l2), max(o[1], e))
+    for kind, (l2, e) in kinds.items():
+        print(f"{tag} {kind}: rel L2 {l2:.3e} element {e:.3e}")
+        record(f"{tag}::{kind}", rel_l2=l2, elem=e)
+
+
+VIT_L14_2LAYERS = V.VitConfig(224, 14, 1024, 2, 16, 768)
+_autograd_fp64_cache = {}
+
+
+def autograd_fp64(cfg, w, x, cot):
+    """Every parameter gradient of sum(vit_forward(x) * cot) by CPU autograd in fp64."""
+    wr = {k: v.double().requires_grad_(True) for k, v in w.items()}
+    e = V.vit_forward(cfg, wr, V.normalize_pixels(x.double()))
+    (e * cot.double()).sum().backward()
+    return {k: v.grad for k, v in wr.items()}
+
+
+# Bars per precision: (per-tensor relative L2, per-element error over max(|reference|, the tensor's RMS), the same for
+# positional_embedding - a sum of only B terms per element, so less of the rounding noise averages out).  Each is the worst value of
+# the first run on an MI355X times 3 to 3.5.  Measured: fp32 1.7e-6 (conv1.weight), 2.8e-5 (c_fc.weight), 3.6e-5 - the fp32 forward
+# and backward against fp64, not summation order alone; bf16 6.2e-3 (ln_1.weight), 3.3e-2 (ln_2.weight), 9.9e-2.
+C1_BARS = {"fp32": (6e-6, 1e-4, 1.2e-4), "bf16": (2e-2, 0.1, 0.3)}
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("B,rows,nch", [(15, 3855, 16), (16, 4112, 128)])
+def test_weight_gradients_across_the_chunk_regime_boundary(B, rows, nch, precision):
+    """Two layers at ViT-L/14's width and sequence length on either side of the 4 096-row boundary: B = 15 (3 855 rows, 16 chunks) and
+    B = 16 (4 112 rows, 128 chunks of 33 rows - the last short, three empty), every parameter gradient against fp64 autograd of the
+    oracle.  Independent images and a cotangent far from zero, as in test_train_step_vit_l14_vs_oracle.  fp32: every element of every
+    tensor; bf16: every tensor by relative L2 (the forward's bf16 rounding is in it) and the reduction-produced tensors per element."""
+    from tests.gpu_helpers import record, assert_elems
+    torch.set_num_threads(16)
+    cfg = VIT_L14_2LAYERS
+    assert B * 257 == rows and L.load().rvlm_k_reduce_chunks(rows) == nch
+    w = V.init_weights(cfg, seed=5)
+    g = torch.Generator().manual_seed(40 + B)
+    x = torch.rand(B, 3, 224, 224, generator=g)
+    cot = torch.randn(B, cfg.out_dim, generator=g)
+    if B not in _autograd_fp64_cache:
+        _autograd_fp64_cache[B] = autograd_fp64(cfg, w, x, cot)
+    ref = _autograd_fp64_cache[B]
+    eng = R.VitEngine(to_cfg(cfg), {k: v.to(dev()) for k, v in w.items()}, precision=precision, max_batch=B, trainable=True)
+    try:
+        grads = FlatParams(to_cfg(cfg), None, dev())
+        grads.flat.fill_(float("nan"))                      # accumulate = False must not read what is there
+        eng.forward(x.to(dev()), None, False, save=2)
+        eng.backward_params(cot.to(dev()), grads.views, accumulate=False)
+        torch.cuda.synchronize()
+        bar_l2, bar_el, bar_pos = C1_BARS[precision]
+        worst_l2, worst_el, worst_l2_key, worst_el_key, rows_ = 0.0, 0.0, None, None, []
+        for k, r in ref.items():
+            got = grads.views[k].cpu()
+            l2 = tensor_rel_l2(got, r)
+            e = 0.0
+            if l2 > worst_l2:
+                worst_l2, worst_l2_key = l2, k
+            assert l2 < bar_l2, f"{k}: relative L2 {l2:.3e}"
+            if precision == "fp32" or reduction_produced(k):
+                e = assert_elems(f"{k} (B = {B}, {precision})", got, r, r.pow(2).mean().sqrt(), bar_pos if k == "positional_embedding" else bar_el,
+                                 dims=("i", "j", "k", "l"))
+                if e > worst_el:
+                    worst_el, worst_el_key = e, k
+            rows_.append((k, l2, e))
+        record(f"weight_gradients_chunk_boundary[{precision}-B{B}]", worst_rel_l2=worst_l2, worst_elem=worst_el)
+        record_by_kind(f"weight_gradients_chunk_boundary[{precision}-B{B}]", rows_)
+        print(f"\nC1 {precision} B {B}: worst rel L2 {worst_l2:.3e} ({worst_l2_key}), worst element {worst_el:.3e} ({worst_el_key})")
+    finally:
+        eng.close()
+        torch.set_num_threads(8)
+
+
+# Bars per precision, as above, of (whole batch) against (32 accumulated slices); measured worst values times 3.
+# fp32: 3.4e-6 (the GEMM-produced tensors: another split-K plan; the reduction-produced ones 2.8e-7), 1.8e-6 (ln_2.weight), 6.5e-6.
+# bf16: 4.9e-3 (ln_2.weight of block 1), 3.0e-2, 8.0e-2.  That is no summation-order figure, and it is not the reductions': the head's
+# tensors, above the first bf16 rounding, agree to 1.2e-4 and ln_post.bias to 1.6e-7; below, a difference d between two runs flips a
+# fraction d / ulp of the next bf16 roundings by one ulp each, which leaves sqrt(d ulp) - 1e-6 becomes 6e-5, then 5e-4, then the
+# rounding noise itself (the by-block record shows it level off).  Two orders of fp32 summation decorrelate the bf16 roundings
+# within a few layers, so the two forms differ by about the engine's own distance from the oracle at this depth.
+C2_BARS = {"fp32": (1e-5, 2e-5, 2e-5), "bf16": (1.5e-2, 0.09, 0.24)}
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_weight_gradients_batch_additivity_at_the_bench_shape(precision):
+    """ViT-L/14 at B = 128 - the training step bench.py --mode train times, M = 32 896 token rows - against the SAME gradient summed
+    from 32 slices of 4 images (accumulate = True into a second flat buffer).  The weight gradient is linear in the per-image
+    cotangent, so the two must agree to summation order (bf16: and to the roundings a different split-K plan moves); the slices are
+    the regime test_train_step_vit_l14_vs_oracle pins against the oracle, and everything that depends on the row count differs between
+    the two forms: the chunk regime of the reductions (16 against 128), the split-K plan of the weight-gradient GEMMs, the tail's M.
+    A row dropped or counted twice at M = 32 896 fails here; no CPU oracle of this size is needed."""
+    from tests.gpu_helpers import record, assert_elems
+    cfg = V.VIT_L_14
+    w = V.init_weights(cfg, seed=3)
+    g = torch.Generator().manual_seed(9)
+    B, nb = 128, 4
+    x = torch.rand(B, 3, 224, 224, generator=g).to(dev())
+    cot = torch.randn(B, cfg.out_dim, generator=g).to(dev())
+    assert L.load().rvlm_k_reduce_chunks(B * 257) == 128 and L.load().rvlm_k_reduce_chunks(nb * 257) == 16
+    eng = R.VitEngine(to_cfg(cfg), {k: v.to(dev()) for k, v in w.items()}, precision=precision, max_batch=B, trainable=True)
+    try:
+        whole, sliced = FlatParams(to_cfg(cfg), None, dev()), FlatParams(to_cfg(cfg), None, dev())
+        whole.flat.fill_(float("nan"))
+        eng.forward(x, None, False, save=2)
+        eng.backward_params(cot, whole.views, accumulate=False)
+        for i in range(0, B, nb):
+            eng.forward(x[i:i + nb], None, False, save=2)
+            eng.backward_params(cot[i:i + nb], sliced.views, accumulate=True)
+        torch.cuda.synchronize()
+        bar_l2, bar_el, bar_pos = C2_BARS[precision]
+        worst_l2, worst_el, worst_l2_key, worst_el_key, rows = 0.0, 0.0, None, None, []
+        for k in whole.views:
+            a, b = whole.views[k], sliced.views[k]
+            l2 = tensor_rel_l2(a, b)
+            e = 0.0
+            if l2 > worst_l2:
+                worst_l2, worst_l2_key = l2, k
+            assert l2 < bar_l2, f"{k}: relative L2 {l2:.3e} between the whole batch and its 32 slices"
+            if reduction_produced(k):
+                e = assert_elems(f"{k} (whole batch against slices, {precision})", a, b, b.double().pow(2).mean().sqrt(),
+                                 bar_pos if k == "positional_embedding" else bar_el, dims=("i", "j", "k", "l"))
+                if e > worst_el:
+                    worst_el, worst_el_key = e, k
+            rows.append((k, l2, e))
+        record(f"weight_gradients_batch_additivity[{precision}]", worst_rel_l2=worst_l2, worst_elem=worst_el)
+        print(f"\nC2 {precision}: worst rel L2 {worst_l2:.3e} ({worst_l2_key}), worst element {worst_el:.3e} ({worst_el_key})")
+        record_by_kind(f"weight_gradients_batch_additivity[{precision}]", rows)
+        by_block = {f"block{int(k.split('.')[2]):02d}": l2 for k, l2, _ in rows if k.endswith("mlp.c_fc.weight")}
+        record(f"weight_gradients_batch_additivity[{precision}]::mlp.c_fc.weight by block", **by_block)
+    finally:
+        eng.close()
