@@ -38,6 +38,9 @@ extern "C" {
  * rvlm_vit_backward_input_tokens, rvlm_tokens_l2_loss_grad, rvlm_vit_tokens_fwd_inputgrad, rvlm_pgd_run_tokens,
  * RVLM_TOKENS_ALL / RVLM_TOKENS_PATCH and RVLM_FLAG_TOKENS_NONFINITE */
 #define RVLM_HAS_TOKENS 1
+/* RVLM_HAS_VLM_ATTACKS: the per-iteration kernels of vlm_eval/attacks/pgd.py / apgd.py on a [B, n_img, P] tensor with a per-image
+ * mask - rvlm_mask_grad, rvlm_pgd_masked_update, rvlm_apgd_masked_step, rvlm_apgd_masked_bookkeeping */
+#define RVLM_HAS_VLM_ATTACKS 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -442,6 +445,47 @@ int rvlm_vit_tokens_fwd_inputgrad(rvlm_vit* h, const float* x, const float* delt
 int rvlm_pgd_run_tokens(rvlm_vit* h, const float* x, const float* delta0, int B, int depth, int ln_post, int select,
                         const float* ref_tokens, int reduction, int norm_kind, float eps, int iterations, float stepsize,
                         float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags, rvlm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * VLM-side attacks (RVLM_HAS_VLM_ATTACKS): the arithmetic of one iteration of vlm_eval/attacks/pgd.py (class PGD) and apgd.py
+ * (apgd) - everything but the model's forward and backward.  The attacked tensor is contiguous fp32 [B, n_img, P] (the reference's
+ * [B, n_img, 1, 3, H, W]; P = elements of one image), `mask` is uint8 [n_img]: 1 = attacked, 0 = masked out (mask_out =
+ * 'context' -> 0...01, 'query' -> 1...10, an int -> that entry 0); NULL = every image attacked.  A masked gradient is g * 0 as in
+ * the reference (NaN / Inf stay NaN), masked images are stepped along that zero gradient and projected with their sample, not
+ * skipped: they come out bit-identical to what went in for L-inf when they lie in the eps-ball and [0,1] (every output of these
+ * calls does), for L2 when they equal x.  16-byte accesses when P % 4 == 0 and the pointers are 16-byte aligned.  B * n_img <= 65535.
+ * norm_kind: 0 = L-inf, 2 = L2 (anything else: RVLM_ERR_UNSUPPORTED; the reference's L1 / L0 branches are not covered).  The L2 forms
+ * run one workgroup per sample with fixed-order fp32 sums (bit-reproducible; equal to torch to fp32 rounding of the norms).
+ * flags: optional device word, RVLM_FLAG_*.
+ * ------------------------------------------------------------------------------------------- */
+/* out = mask * grad (pgd.py:40, apgd.py:223-224,303-304); out may be grad.  flags |= RVLM_FLAG_NAN_GRAD if the product holds a
+ * NaN (it is left in place: apgd keeps it; rvlm_pgd_masked_update zeroes it itself). */
+int rvlm_mask_grad(const float* grad, const uint8_t* mask, int B, int n_img, size_t P, float* out, int32_t* flags,
+                   rvlm_stream_t stream);
+/* One iteration of PGD.perturb after the gradient (pgd.py:39-65): g = mask * grad, NaN -> 0 (RVLM_FLAG_NAN_GRAD), normalize_grad
+ * (sign | g / max(|g|_2, 1e-12) per sample, the norm over the MASKED gradient), velocity = normalize(momentum * velocity + g),
+ * delta -+= stepsize * velocity (mode_max = 0: minimise), project_perturbation (clamp to +-eps | torch.renorm to eps), and if
+ * image_space: delta = clamp(x + delta, 0, 1) - x with RVLM_FLAG_ADV_RANGE where x + delta leaves (-1e-6, 1 + 1e-6) (:62-64).
+ * RVLM_FLAG_NAN_DELTA: NaN in delta (:65).  grad is the RAW gradient.  x_adv_out (optional) = x + delta. */
+int rvlm_pgd_masked_update(const float* x, const float* grad, float* delta, float* velocity, const uint8_t* mask, int B, int n_img,
+                           size_t P, int norm_kind, float eps, float stepsize, float momentum, int mode_max, int image_space,
+                           float* x_adv_out, int32_t* flags, rvlm_stream_t stream);
+/* One gradient step of apgd (apgd.py:242-266): momentum step with a = 1.0 (first iteration) | 0.75, both projections, x_adv_old
+ * <- x_adv, x_adv <- the new point; step [B] is read from device memory.  grad may be the raw or the already masked gradient (the
+ * mask is applied here; mask * mask = mask).  flags |= RVLM_FLAG_NAN_GRAD for a NaN in mask * grad (not zeroed: the reference
+ * does not). */
+int rvlm_apgd_masked_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const uint8_t* mask, const float* step,
+                          float a, float eps, int B, int n_img, size_t P, int norm_kind, int32_t* flags, rvlm_stream_t stream);
+/* apgd.py:321-351 for iteration i with [B] losses: loss_steps[i] = loss_i, the best-loss select of x_best / grad_best / loss_best,
+ * x_best_adv = x_adv (:310), and at a checkpoint (do_check; the host knows k and counter3, they do not depend on data) the
+ * oscillation test, step halving and restart of x_adv / grad from x_best / grad_best.  It is rvlm_apgd_controller (rho = 0.75) +
+ * rvlm_apgd_select with "never classified correctly" for every sample - their semantics equal this function's, no kernel of its
+ * own.  scratch: 5 * B bytes, zeroed by the caller before the first iteration and not touched by it between iterations.
+ * loss_steps [n_iter, B]; n_per_sample = n_img * P. */
+int rvlm_apgd_masked_bookkeeping(int i, int B, int n_iter, int k, int do_check, const float* loss_i, float* loss_steps,
+                                 float* loss_best, float* loss_best_last_check, float* reduced_last_check, float* step,
+                                 float* x_adv, float* grad, float* x_best, float* grad_best, float* x_best_adv, uint8_t* scratch,
+                                 size_t n_per_sample, rvlm_stream_t stream);
 
 /* APGD L-inf.  x_init: NULL -> start from clamp(x,0,1) (apgd_train) or the caller-provided random
  * start (APGDAttack).  logits_from_head: 0 -> the `argmax(model output)==y` test runs on the

@@ -292,6 +292,14 @@ _SIGS.update({
                                                 c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rvlm_pgd_run_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int,
                                       C.c_float, C.c_int, C.c_float, C.c_float, C.c_int, c_f32p, c_f32p, C.c_void_p, c_stream]),
+    # ---- VLM-side attacks (RVLM_HAS_VLM_ATTACKS) ----
+    "rvlm_mask_grad": (C.c_int, [c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, c_f32p, C.c_void_p, c_stream]),
+    "rvlm_pgd_masked_update": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_float,
+                                         C.c_float, C.c_float, C.c_int, C.c_int, c_f32p, C.c_void_p, c_stream]),
+    "rvlm_apgd_masked_step": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, C.c_float, C.c_float, C.c_int, C.c_int,
+                                        C.c_size_t, C.c_int, C.c_void_p, c_stream]),
+    "rvlm_apgd_masked_bookkeeping": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                               c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "rvlm_k_tokens_seed": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
 })
 _SIGS.update({
