@@ -53,32 +53,16 @@ int rvlm_k_attn_set_use_tr(int on);
  * few-row rule sends the shape to the 128x128 kernel); 3: persistent kernel for every shape it can take (M >= 256,
  * N % 256 == 0, K % 128 == 0) regardless of those rules; -1: env RVLM_GEMM_VARIANT (default 2) */
 int rvlm_k_gemm_set_variant(int v);
-/* Bit mask of the kernel families the last rvlm_k_gemm_bf16_nt call (or the engine's last GEMM) launched */
+/* Bit mask of the kernel families the last rvlm_k_gemm_bf16_nt call (or the engine's last GEMM) launched (bits 2, 8 and 64
+ * named kernels that left the tree and stay unused) */
 #define RVLM_GEMM_K_128 1         /* gemm_bf16_nt_kernel, 128x128 tiles */
-#define RVLM_GEMM_K_256 2         /* one-tile-per-workgroup 256x256 kernel (EXPERIMENTAL builds only) */
 #define RVLM_GEMM_K_PERSISTENT 4  /* gemm_bf16_nt_256p_kernel, the persistent 256x256 kernel */
-#define RVLM_GEMM_K_256Q 8        /* 4-wave persistent kernel (EXPERIMENTAL builds only) */
 #define RVLM_GEMM_K_SPLITK 16     /* split-K slabs on the 128x128 kernel + splitk_reduce_kernel */
 #define RVLM_GEMM_K_STRIP 32      /* remainder rows computed by the persistent kernel's strip phase (same launch) */
-#define RVLM_GEMM_K_PINGPONG 64   /* gemm_bf16_nt_256x_kernel, the persistent kernel with phase-shifted wave groups */
 int rvlm_k_gemm_last_kernels(void);
 /* persistent 256x256 kernel: device buffer of 256*8*4 uint64 receiving per-tile s_memtime stamps (tile start, first
  * K-step done, mainloop done, epilogue issued); NULL switches tracing off */
 int rvlm_k_gemm_set_trace(void* ptr);
-/* Phase-shifted (ping-pong) persistent kernel, gemm_bf16_256x.hip: `mask` bit e sends epilogue kind e (0 bf16, 1 fp32 +
- * residual, 2 activation pair, 3 x stored act', 4 fp32) to it for K <= kmax when the shape qualifies; mask < 0 restores
- * the environment / default (RVLM_GEMM_PINGPONG, RVLM_GEMM_PINGPONG_KMAX).  rvlm_k_gemm_x_set_trace: device buffer of
- * 256 * 8 * 26 uint64 receiving, per workgroup and wave, s_memtime at kernel start / end and at the start of the MFMAs,
- * the end of the MFMAs and the end of the epilogue of the wave's first 8 tiles; NULL switches tracing off. */
-int rvlm_k_gemm_set_pingpong(int mask, int kmax);
-int rvlm_k_gemm_x_set_trace(void* ptr);
-/* persistent kernel timing experiments (results become garbage): bit 0 no operand DMA, bit 1 no MFMA, bit 2 no LDS
- * fragment reads; 0 = normal */
-int rvlm_k_gemm_set_ablate(int v);
-/* MFMA shape of the persistent kernel's tile phase: 1 = v_mfma_f32_16x16x32_bf16 (8 x 4 accumulator tiles per wave; the
- * shipped form since round 4), 0 = v_mfma_f32_32x32x16_bf16 (4 x 2; EXPERIMENTAL builds only, RVLM_ERR_UNSUPPORTED otherwise),
- * -1 = environment / build default (RVLM_GEMM_M16).  Same results to fp32 summation order. */
-int rvlm_k_gemm_set_m16(int v);
 /* measurement only: the persistent GEMM's operand request stream (same tile order, 8 waves x (4 + 4) pieces of 8 rows x
  * 128 B per K-step) with no MFMA and no LDS, `depth` K-steps (depth x 64 KiB per CU) in flight in registers.
  * mode bit 0: one s_barrier per K-step (a wave waits for the slowest wave's pieces, like a GEMM K-step); bit 1: pieces by

@@ -176,13 +176,10 @@ extern "C" int rvlm_vit_create(const rvlm_vit_config* cfg, const rvlm_vit_weight
             if (h->lin.bf16) {
                 // What the copy-free contraction-major weight gradient leaves to these buffers: conv1 (max(W, Kpad) rows x all tokens),
                 // and every linear when fewer than 256 tokens are in flight (4W rows x < 320 columns, short leading dimension).
-                // Widths that are no multiple of 256 - and the EXPERIMENTAL build's transposing A/B arm - transpose every linear:
+                // Widths that are no multiple of 256 transpose every linear:
                 // 4W rows x all tokens (0.57 GB for ViT-L/14 at B = 128).
                 h->Mpt = (long)Mp + 16 * 128;
-                bool every_linear = W % 256 != 0;
-#ifdef RVLM_EXPERIMENTAL_GEMM
-                every_linear = true;
-#endif
+                const bool every_linear = W % 256 != 0;
                 const size_t rows = (size_t)(every_linear ? std::max(4 * W, h->Kpad) : std::max(W, h->Kpad));
                 h->t_elems = std::max(rows * (size_t)h->Mpt, (size_t)std::max(4 * W, h->Kpad) * 320);
                 ALLOC(h->tA, h->t_elems * 2);

@@ -185,98 +185,59 @@ splitk_reduce_kernel(const float* __restrict__ slabs, int splitk, GemmBf16 p) {
 
 
 int gemm_bf16_nt_256p(const GemmBf16& p, int* rows_done, hipStream_t s);
-int gemm_bf16_nt_256x(const GemmBf16& p, int* rows_done, hipStream_t s);
-#ifdef RVLM_EXPERIMENTAL_GEMM   // ablation kernels (make EXPERIMENTAL=1): not part of the shipped library
-int gemm_bf16_nt_256(const GemmBf16& p, int* rows_done, hipStream_t s);
-int gemm_bf16_nt_256q(const GemmBf16& p, int* rows_done, hipStream_t s);
-#endif
 
 // Which kernel families the last gemm_bf16_nt() call launched (test surface: rvlm_k_gemm_last_kernels): the parity
 // tests assert that the family they name is the one that ran - a dispatch rule must not silently move them.
 static int g_last_kernels = 0;
 int gemm_last_kernels() { return g_last_kernels; }
 
-static int g_waves = -1;   // persistent kernel flavour: 8 waves x 128x64 (default) or 4 waves x 128x128
-static int gemm_waves() {
-    if (g_waves < 0) { const char* e = getenv("RVLM_GEMM_WAVES"); g_waves = e ? atoi(e) : 8; }
-    return g_waves;
+// The environment's switches, each read once.  RVLM_GEMM_VARIANT 0: 128x128 kernel only; 1 / 2 (default, the same): persistent
+// 256x256 kernel where the shape qualifies and neither the few-row rule nor the fill rule below objects; 3: persistent kernel
+// for EVERY shape it can take (M >= 256, N % 256 == 0, K % 128 == 0), both rules off - the parity tests of the persistent
+// kernel run under 3.  (RVLM_GEMM_TAIL is read where it acts, in gemm_bf16_256p.hip.)
+struct GemmEnv { int variant, desync; float min_fill; };
+static const GemmEnv& gemm_env() {
+    static const char* const fill = getenv("RVLM_GEMM_MIN_FILL");
+    static const GemmEnv e = {env_int("RVLM_GEMM_VARIANT", 2), env_int("RVLM_GEMM_DESYNC", 0), fill ? (float)atof(fill) : 0.7f};
+    return e;
 }
-
-static int g_persist = -1;
-static int gemm_persist() {
-    if (g_persist < 0) { const char* e = getenv("RVLM_GEMM_PERSIST"); g_persist = e ? atoi(e) : 1; }
-    return g_persist;
-}
-
-// 0: 128x128 kernel only; 1 / 2 (default): persistent 256x256 kernel where the shape qualifies and the fill rule
-// below does not send it to the 128x128 kernel; 3: persistent kernel for EVERY shape it can take (M >= 256,
-// N % 256 == 0, K % 128 == 0), fill rule and few-row rule off - the parity tests of the persistent kernel run under 3.
-// (EXPERIMENTAL builds with RVLM_GEMM_PERSIST=0: the older per-shape choice between the one-tile-per-workgroup 256x256
-// kernel and the 128x128 kernel.)
-static int g_gemm_variant = -1;
+static int g_gemm_variant = -1;   // rvlm_k_gemm_set_variant; < 0: the environment's
 void gemm_set_variant(int v) { g_gemm_variant = v; }
-// RVLM_GEMM_PINGPONG: bit mask over epilogue kinds (GemmEpi) that take gemm_bf16_256x.hip; RVLM_GEMM_PINGPONG_KMAX: largest K
-static int g_pingpong_mask = -1, g_pingpong_kmax = -1;
-static int gemm_pingpong_mask() {
-    if (g_pingpong_mask < 0) { const char* e = getenv("RVLM_GEMM_PINGPONG"); g_pingpong_mask = e ? atoi(e) : RVLM_PINGPONG_DEFAULT_MASK; }
-    return g_pingpong_mask;
-}
-static int gemm_pingpong_kmax() {
-    if (g_pingpong_kmax < 0) { const char* e = getenv("RVLM_GEMM_PINGPONG_KMAX"); g_pingpong_kmax = e ? atoi(e) : RVLM_PINGPONG_DEFAULT_KMAX; }
-    return g_pingpong_kmax;
-}
-// mask < 0: back to the environment / default for BOTH values (whatever kmax says)
-void gemm_set_pingpong(int mask, int kmax) {
-    if (mask < 0) { g_pingpong_mask = -1; g_pingpong_kmax = -1; }
-    else { g_pingpong_mask = mask; g_pingpong_kmax = kmax; }
-}
-bool gemm_has_pingpong() {
-#ifdef RVLM_EXPERIMENTAL_GEMM
-    return true;
-#else
-    return false;
-#endif
-}
-static int gemm_variant() {
-    if (g_gemm_variant < 0) {
-        const char* e = getenv("RVLM_GEMM_VARIANT");
-        g_gemm_variant = e ? atoi(e) : 2;
-    }
-    return g_gemm_variant;
-}
-
-static int g_desync = -1;
-static int gemm_desync() {
-    if (g_desync < 0) { const char* e = getenv("RVLM_GEMM_DESYNC"); g_desync = e ? atoi(e) : 0; }
-    return g_desync;
-}
+static int gemm_variant() { return g_gemm_variant >= 0 ? g_gemm_variant : gemm_env().variant; }
 
 static int gemm_bf16_nt_128(const GemmBf16& p, hipStream_t s) {
-    const int desync = gemm_desync();
+    const int desync = gemm_env().desync;
     const int tiles_m = cdiv(p.M, GB_M), tiles_n = cdiv(p.N, GB_N);
     const int a_rows = p.a_rows > 0 ? p.a_rows : p.M;
-    dim3 grid(tiles_m * tiles_n), block(256);
-    switch (p.epi) {
-        case EPI_BF16:
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_BF16>), grid, block, 0, s, p, tiles_m, tiles_n, a_rows, desync);
-            break;
-        case EPI_F32_RESID:
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_F32_RESID>), grid, block, 0, s, p, tiles_m, tiles_n, a_rows, desync);
-            break;
-        case EPI_BF16_ACT:
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_BF16_ACT>), grid, block, 0, s, p, tiles_m, tiles_n, a_rows, desync);
-            break;
-        case EPI_BF16_DACT:
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_BF16_DACT>), grid, block, 0, s, p, tiles_m, tiles_n, a_rows, desync);
-            break;
-        case EPI_F32:
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_F32>), grid, block, 0, s, p, tiles_m, tiles_n, a_rows, desync);
-            break;
-        default:
-            return fail(RVLM_ERR_ARG, "gemm_bf16_nt: unknown epilogue");
-    }
+    return with_epi(p.epi, [&](auto epi) -> int {
+        hipLaunchKernelGGL((gemm_bf16_nt_kernel<decltype(epi)::value>), dim3(tiles_m * tiles_n), dim3(256), 0, s, p, tiles_m, tiles_n,
+                           a_rows, desync);
+        RVLM_CHECK_LAUNCH();
+        return RVLM_OK;
+    });
+}
+
+// fp32 slabs [splitk][r.M][r.N] -> their sum in slab order, then r's epilogue (bias, residual, activation ...) into r.out
+static int splitk_reduce(const float* slabs, int splitk, const GemmBf16& r, hipStream_t s) {
+    const int rb = cdiv((long)r.M * (r.N / 4), 256);
+    return with_epi(r.epi, [&](auto epi) -> int {
+        hipLaunchKernelGGL((splitk_reduce_kernel<decltype(epi)::value>), dim3(rb), dim3(256), 0, s, slabs, splitk, r);
+        RVLM_CHECK_LAUNCH();
+        return RVLM_OK;
+    });
+}
+// Split-K on the 128x128 kernel: gridDim.y = splitk slices of K leave fp32 partial sums in the slabs of r.splitk, the reduce
+// kernel finishes r
+static int gemm_bf16_nt_splitk(const GemmBf16& r, int splitk, hipStream_t s) {
+    GemmBf16 part = r;
+    part.epi = EPI_F32; part.bias = nullptr; part.residual = nullptr; part.out = r.splitk;
+    part.ldo = r.N; part.out_pre = nullptr; part.h_pre = nullptr;
+    part.a_rows = r.a_rows > 0 ? r.a_rows : r.M;
+    const int tiles_m = cdiv(r.M, GB_M), tiles_n = cdiv(r.N, GB_N);
+    hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_F32>), dim3(tiles_m * tiles_n, splitk), dim3(256), 0, s, part, tiles_m, tiles_n,
+                       part.a_rows, 0);
     RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
+    return splitk_reduce(r.splitk, splitk, r, s);
 }
 
 // Split-K weight gradient on the persistent kernel.  dW[N,K] (+)= sum_b tA_b tB_b^T with tA = [splits][N][Kc] and
@@ -302,6 +263,13 @@ int wgrad_split_plan(int M, int N, int K, size_t slab_bytes, int* splits, int* K
     *Kc = cdiv(nk128, sp) * 128;
     return 1;
 }
+// the weight gradient's slabs [splits][N][K] -> dW (+)= their sum
+static int wgrad_reduce(const float* slab, int splits, int N, int K, float* dW, long lddw, int accumulate, hipStream_t s) {
+    GemmBf16 r;
+    r.M = N; r.N = K; r.out = dW; r.ldo = lddw;
+    r.epi = accumulate ? EPI_F32_RESID : EPI_F32; r.residual = accumulate ? dW : nullptr;
+    return splitk_reduce(slab, splits, r, s);
+}
 int gemm_bf16_wgrad_split(const bf16_t* tA, const bf16_t* tB, int splits, int Kc, int N, int K, float* dW, long lddw,
                           int accumulate, float* slab, size_t slab_bytes, hipStream_t s) {
     if (splits > 1 && (!slab || (size_t)splits * N * K * sizeof(float) > slab_bytes))
@@ -320,17 +288,7 @@ int gemm_bf16_wgrad_split(const bf16_t* tA, const bf16_t* tB, int splits, int Kc
     int rc = gemm_bf16_nt_256p(g, &done, s);
     if (rc) return rc;
     if (done != g.M) return fail(RVLM_ERR_UNSUPPORTED, "gemm_bf16_wgrad_split: shape not covered by the persistent kernel");
-    if (splits > 1) {
-        GemmBf16 r;
-        r.M = N; r.N = K; r.out = dW; r.ldo = lddw; r.residual = accumulate ? dW : nullptr;
-        const int rb = cdiv((long)N * (K / 4), 256);
-        if (accumulate)
-            hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32_RESID>), dim3(rb), dim3(256), 0, s, slab, splits, r);
-        else
-            hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32>), dim3(rb), dim3(256), 0, s, slab, splits, r);
-        RVLM_CHECK_LAUNCH();
-    }
-    return RVLM_OK;
+    return splits > 1 ? wgrad_reduce(slab, splits, N, K, dW, lddw, accumulate, s) : RVLM_OK;
 }
 
 // Weight gradient without operand copies: the persistent kernel's contraction-major form (gemm_bf16_256p.hip, TN) reads dY and X
@@ -368,15 +326,65 @@ int gemm_bf16_wgrad_tn(const bf16_t* dY, long lddy, const bf16_t* X, long ldx, i
     int rc = gemm_bf16_nt_256p(g, &done, s);
     if (rc) return rc;
     if (done != g.M) return fail(RVLM_ERR_UNSUPPORTED, "gemm_bf16_wgrad_tn: shape not covered by the persistent kernel");
-    GemmBf16 r;
-    r.M = N; r.N = K; r.out = dW; r.ldo = lddw; r.residual = accumulate ? dW : nullptr;
-    const int rb = cdiv((long)N * (K / 4), 256);
-    if (accumulate)
-        hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32_RESID>), dim3(rb), dim3(256), 0, s, slab, splits, r);
-    else
-        hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32>), dim3(rb), dim3(256), 0, s, slab, splits, r);
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
+    return wgrad_reduce(slab, splits, N, K, dW, lddw, accumulate, s);
+}
+
+// ---- the dispatch rule -------------------------------------------------------------------------------------------------
+// Deep-K, few-tile fp32 problems (the weight-gradient GEMMs on the transposing path: K = all tokens, <= 256 output tiles): split
+// K so that >= 2 workgroups per CU are busy.  The largest fitting candidate up to the first that reaches 512 workgroups; 1: none.
+static int splitk_deep_k(const GemmBf16& p) {
+    if (p.K < 8192 || (p.epi != EPI_F32 && p.epi != EPI_F32_RESID) || !p.splitk) return 1;
+    const int tiles = cdiv(p.M, GB_M) * cdiv(p.N, GB_N), nk64 = p.K / GB_K;
+    int splitk = 1;
+    for (int cand : {2, 3, 4, 6, 12}) {
+        if (nk64 % cand == 0 && (size_t)cand * p.M * p.N * sizeof(float) <= p.splitk_bytes) {
+            splitk = cand;
+            if (tiles * cand >= 512) break;
+        }
+    }
+    return splitk;
+}
+// Few rows r (the class-token tail: M = batch rows; with RVLM_GEMM_TAIL=0 also the <= 255 remainder rows of a big problem) are a
+// handful of 128x128 tiles walking K serially (~1 us per 64-deep step, latency-bound).  Cut K so that >= 128 workgroups share the
+// walk, at most 512, each keeping >= 2 K-steps; 1: none.
+static int splitk_few_rows(const GemmBf16& r) {
+    if (r.M > 512 || !r.splitk) return 1;
+    const int nk64 = r.K / GB_K, tiles = cdiv(r.M, GB_M) * cdiv(r.N, GB_N);
+    int splitk = 1;
+    for (int cand : {2, 3, 4, 6, 8, 12, 16}) {
+        if (nk64 % cand != 0 || nk64 / cand < 2 || tiles * cand > 512) continue;
+        if ((size_t)cand * r.M * r.N * sizeof(float) > r.splitk_bytes) continue;
+        splitk = cand;
+        if (tiles * cand >= 128) break;
+    }
+    return splitk;
+}
+// few-row rule (the class-token rows of the last block: M = batch): a handful of 256x256 tiles cannot fill the chip - they
+// take the 128x128 kernel, split-K
+static bool few_rows(const GemmBf16& p) { return p.M <= 512; }
+// fill rule - how full the persistent kernel's rounds of <= 256 tiles would be: a small problem (ViT-B/32 at batch 128: 75-300
+// tiles) leaves most CUs idle or runs a nearly empty last round - the 128x128 kernel (4x the tiles, 2 workgroups per CU) then
+// wins (+17 % on that model) although its mainloop is slower.  Deep-K tiles amortise the persistent kernel's per-tile cost:
+// there only a really empty chip (< 45 %) switches.
+static bool sparse_fill(const GemmBf16& p) {
+    if (p.N % 256 != 0 || p.M < 256) return false;
+    const long t256 = (long)(p.M / 256) * (p.N / 256);
+    const float fill = (float)t256 / (float)(((t256 + 255) / 256) * 256);
+    return fill < 0.45f || (fill < gemm_env().min_fill && p.K <= 1024);
+}
+// rows [done, M) of p as a problem of their own
+static GemmBf16 remainder_rows(const GemmBf16& p, int done) {
+    GemmBf16 r = p;
+    if (done == 0) return r;
+    const bool f32out = (p.epi == EPI_F32_RESID || p.epi == EPI_F32);
+    r.A = p.A + (long)done * p.lda;
+    r.out = (char*)p.out + (long)done * p.ldo * (f32out ? 4 : 2);
+    if (p.out_pre) r.out_pre = p.out_pre + (long)done * p.ldo;
+    if (p.h_pre) r.h_pre = p.h_pre + (long)done * p.ldo;
+    if (p.residual) r.residual = p.residual + (long)done * p.ldo;
+    r.M = p.M - done;
+    r.a_rows = (p.a_rows > 0 ? p.a_rows : p.M) - done;
+    return r;
 }
 
 int gemm_bf16_nt(const GemmBf16& p, hipStream_t s) {
@@ -384,140 +392,29 @@ int gemm_bf16_nt(const GemmBf16& p, hipStream_t s) {
         return fail(RVLM_ERR_ARG, "gemm_bf16_nt: bad arguments");
     if (p.K % GB_K != 0 || p.N % 4 != 0 || p.lda % 8 != 0 || p.ldb % 8 != 0 || p.ldo % 4 != 0)
         return fail(RVLM_ERR_UNSUPPORTED, "gemm_bf16_nt: need K%64==0, N%4==0, lda/ldb%8==0, ldo%4==0");
+    if (p.epi < EPI_BF16 || p.epi > EPI_F32) return fail(RVLM_ERR_ARG, "gemm_bf16_nt: unknown epilogue");
     if (p.epi == EPI_BF16_DACT && !p.h_pre) return fail(RVLM_ERR_ARG, "gemm_bf16_nt: h_pre");
-    // deep-K, few-tile problems (the weight-gradient GEMMs: K = all tokens, <= 256 output tiles): split K so
-    // that >= 2 workgroups per CU are busy, fp32 slabs + deterministic reduce/epilogue kernel
-    if (p.K >= 8192 && (p.epi == EPI_F32 || p.epi == EPI_F32_RESID) && p.splitk) {
-        const int tiles = cdiv(p.M, GB_M) * cdiv(p.N, GB_N);
-        int splitk = 1;
-        const int nk64 = p.K / GB_K;
-        for (int cand : {2, 3, 4, 6, 12}) {
-            if (nk64 % cand == 0 && (size_t)cand * p.M * p.N * sizeof(float) <= p.splitk_bytes) {
-                splitk = cand;
-                if (tiles * cand >= 512) break;
-            }
-        }
-        if (splitk > 1) {
-            GemmBf16 part = p;
-            part.epi = EPI_F32; part.bias = nullptr; part.residual = nullptr; part.out = p.splitk;
-            part.ldo = p.N; part.out_pre = nullptr; part.h_pre = nullptr;
-            part.a_rows = p.a_rows > 0 ? p.a_rows : p.M;
-            const int tiles_m = cdiv(p.M, GB_M), tiles_n = cdiv(p.N, GB_N);
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_F32>), dim3(tiles_m * tiles_n, splitk), dim3(256), 0, s, part,
-                               tiles_m, tiles_n, part.a_rows, 0);
-            RVLM_CHECK_LAUNCH();
-            const int rb = cdiv((long)p.M * (p.N / 4), 256);
-            if (p.epi == EPI_F32_RESID)
-                hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32_RESID>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, p);
-            else
-                hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, p);
-            RVLM_CHECK_LAUNCH();
-            g_last_kernels = RVLM_GEMM_K_SPLITK;
-            return RVLM_OK;
-        }
+    if (const int splitk = splitk_deep_k(p); splitk > 1) {
+        g_last_kernels = RVLM_GEMM_K_SPLITK;
+        return gemm_bf16_nt_splitk(p, splitk, s);
     }
-    int done = 0;
-    const int variant = gemm_variant();
     g_last_kernels = 0;
-    // few-row problems (the class-token rows of the last block: M = batch): a handful of 256x256 tiles cannot fill the
-    // chip - they take the 128x128 kernel with split-K below
-    const bool small_m = p.M <= 512 && variant != 3;
-    // 1 or 2 (default): the persistent 256x256 kernel wherever the shape qualifies (N % 256 == 0, K % 128 == 0); it
-    // beats both older kernels on every encoder shape (scripts/gemm_bench.py, profiles/).  RVLM_GEMM_PERSIST=0
-    // restores the per-shape choice between the one-tile-per-workgroup 256x256 kernel and the 128x128 kernel.
-    // how full the persistent kernel's rounds of <= 256 tiles would be: a small problem (ViT-B/32 at batch 128: 75-300
-    // tiles) leaves most CUs idle or runs a nearly empty last round - the 128x128 kernel (4x the tiles, 2 workgroups per
-    // CU) then wins (+17 % on that model) although its mainloop is slower
-    bool sparse = false;
-    if (p.N % 256 == 0 && p.M >= 256) {
-        const long t256 = (long)(p.M / 256) * (p.N / 256);
-        static float min_fill = -1.0f;
-        if (min_fill < 0.0f) { const char* e = getenv("RVLM_GEMM_MIN_FILL"); min_fill = e ? (float)atof(e) : 0.7f; }
-        const float fill = (float)t256 / (float)(((t256 + 255) / 256) * 256);
-        // deep-K tiles amortise the persistent kernel's per-tile cost: there only a really empty chip (< 45 %) switches
-        sparse = variant != 3 && (fill < 0.45f || (fill < min_fill && p.K <= 1024));
-    }
-    if (variant != 0 && gemm_persist() && !small_m && !sparse) {
-        int rc;
-#ifdef RVLM_EXPERIMENTAL_GEMM
-        const bool no_pre = p.epi == EPI_BF16_ACT && !p.out_pre;   // only the default kernel knows the one-output form
-        if (gemm_waves() == 4 && !no_pre) { rc = gemm_bf16_nt_256q(p, &done, s); if (done) g_last_kernels |= RVLM_GEMM_K_256Q; }
-        else
-#endif
-        {
-            rc = RVLM_OK;
-#ifdef RVLM_EXPERIMENTAL_GEMM
-            // the phase-shifted (ping-pong) form of the persistent kernel (experimental/gemm_bf16_256x.hip: bit-identical,
-            // 3-15 % slower, round 3), per epilogue kind (bit e of the mask, e = the kind the kernel will RUN: fp32 +
-            // residual without a residual is the plain fp32 kind) and up to a K limit
-            const int epi_run = (p.epi == EPI_F32_RESID && !p.residual) ? (int)EPI_F32 : (int)p.epi;
-            if (((gemm_pingpong_mask() >> epi_run) & 1) && p.K <= gemm_pingpong_kmax()) {
-                rc = gemm_bf16_nt_256x(p, &done, s);
-                if (done) g_last_kernels |= RVLM_GEMM_K_PINGPONG | (done > (p.M / 256) * 256 ? RVLM_GEMM_K_STRIP : 0);
-            }
-#endif
-            if (!rc && !done) {
-                rc = gemm_bf16_nt_256p(p, &done, s);
-                if (done) g_last_kernels |= RVLM_GEMM_K_PERSISTENT | (done > (p.M / 256) * 256 ? RVLM_GEMM_K_STRIP : 0);
-            }
-        }
-        if (rc) return rc;
+    // the persistent kernel (it beats the 128x128 kernel on every encoder shape: scripts/gemm_bench.py, profiles/) takes the
+    // whole multiples of 256 rows, by default the remainder rows too
+    const int variant = gemm_variant();
+    const bool few = variant != 3 && few_rows(p), sparse = variant != 3 && sparse_fill(p);
+    int done = 0;
+    if (variant != 0 && !few && !sparse) {
+        if (int rc = gemm_bf16_nt_256p(p, &done, s)) return rc;
+        if (done) g_last_kernels |= RVLM_GEMM_K_PERSISTENT | (done > (p.M / 256) * 256 ? RVLM_GEMM_K_STRIP : 0);
         if (done >= p.M) return RVLM_OK;
     }
-#ifdef RVLM_EXPERIMENTAL_GEMM
-    const bool big = variant == 1 || (variant == 2 && (p.epi == EPI_BF16 || p.K >= 2048));
-    if (done == 0 && big && !small_m && !sparse) {
-        int rc = gemm_bf16_nt_256(p, &done, s);
-        if (rc) return rc;
-        if (done) g_last_kernels |= RVLM_GEMM_K_256;
-        if (done >= p.M) return RVLM_OK;
-    }
-#endif
-    GemmBf16 r = p;
-    if (done > 0) {   // remainder rows [done, M) on the 128x128 kernel
-        const bool f32out = (p.epi == EPI_F32_RESID || p.epi == EPI_F32);
-        r.A = p.A + (long)done * p.lda;
-        r.out = (char*)p.out + (long)done * p.ldo * (f32out ? 4 : 2);
-        if (p.out_pre) r.out_pre = p.out_pre + (long)done * p.ldo;
-        if (p.h_pre) r.h_pre = p.h_pre + (long)done * p.ldo;
-        if (p.residual) r.residual = p.residual + (long)done * p.ldo;
-        r.M = p.M - done;
-        r.a_rows = (p.a_rows > 0 ? p.a_rows : p.M) - done;
-    }
-    if ((done > 0 || small_m) && variant != 0) {
-        // split-K: the strip is a handful of 128x128 tiles walking K serially (~1 us per 64-deep step, latency-bound).
-        // Cut K so that >= 128 workgroups share the walk, each keeping >= 2 K-steps; fp32 slabs + reduce/epilogue kernel.
-        int splitk = 1;
-        {
-            const int nk64 = p.K / GB_K, tiles = cdiv(r.M, GB_M) * cdiv(p.N, GB_N);
-            for (int cand : {2, 3, 4, 6, 8, 12, 16}) {
-                if (nk64 % cand != 0 || nk64 / cand < 2 || tiles * cand > 512) continue;
-                if ((size_t)cand * r.M * p.N * sizeof(float) > p.splitk_bytes) continue;
-                splitk = cand;
-                if (tiles * cand >= 128) break;
-            }
-        }
-        const size_t need = (size_t)splitk * r.M * p.N * sizeof(float);
-        if (splitk > 1 && r.M <= 512 && p.splitk && need <= p.splitk_bytes && p.K % (splitk * GB_K) == 0) {
-            GemmBf16 part = r;
-            part.epi = EPI_F32; part.bias = nullptr; part.residual = nullptr; part.out = p.splitk;
-            part.ldo = p.N; part.out_pre = nullptr; part.h_pre = nullptr;
-            part.a_rows = r.a_rows > 0 ? r.a_rows : r.M;
-            const int tiles_m = cdiv(part.M, GB_M), tiles_n = cdiv(part.N, GB_N);
-            hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI_F32>), dim3(tiles_m * tiles_n, splitk), dim3(256), 0, s, part,
-                               tiles_m, tiles_n, part.a_rows, 0);
-            RVLM_CHECK_LAUNCH();
-            const int rb = cdiv((long)r.M * (p.N / 4), 256);
-            switch (p.epi) {
-                case EPI_BF16: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_BF16>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, r); break;
-                case EPI_F32_RESID: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32_RESID>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, r); break;
-                case EPI_BF16_ACT: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_BF16_ACT>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, r); break;
-                case EPI_BF16_DACT: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_BF16_DACT>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, r); break;
-                default: hipLaunchKernelGGL((splitk_reduce_kernel<EPI_F32>), dim3(rb), dim3(256), 0, s, p.splitk, splitk, r); break;
-            }
-            RVLM_CHECK_LAUNCH();
+    // what is left - or everything - on the 128x128 kernel, split-K when it is few rows
+    const GemmBf16 r = remainder_rows(p, done);
+    if ((done > 0 || few) && variant != 0) {
+        if (const int splitk = splitk_few_rows(r); splitk > 1) {
             g_last_kernels |= RVLM_GEMM_K_SPLITK;
-            return RVLM_OK;
+            return gemm_bf16_nt_splitk(r, splitk, s);
         }
     }
     g_last_kernels |= RVLM_GEMM_K_128;

@@ -11,8 +11,22 @@
 // Edge tiles (M or N not a multiple of the wave tile) take the predicated per-lane path.
 #pragma once
 #include "kernels.h"
+#include <type_traits>
 
 namespace rvlm {
+
+// (host) the run-time epilogue kind as a template argument: f(std::integral_constant<int, EPI>{}) for the kind `epi` names
+template <typename F>
+static inline int with_epi(int epi, F&& f) {
+    switch (epi) {
+        case EPI_BF16: return f(std::integral_constant<int, EPI_BF16>{});
+        case EPI_F32_RESID: return f(std::integral_constant<int, EPI_F32_RESID>{});
+        case EPI_BF16_ACT: return f(std::integral_constant<int, EPI_BF16_ACT>{});
+        case EPI_BF16_DACT: return f(std::integral_constant<int, EPI_BF16_DACT>{});
+        case EPI_F32: return f(std::integral_constant<int, EPI_F32>{});
+    }
+    return fail(RVLM_ERR_ARG, "bf16 GEMM: unknown epilogue");
+}
 
 constexpr int EPI_LDS_BYTES_PER_WAVE = 32 * 272;   // 32 rows x (64 fp32 + 16 B pad)
 

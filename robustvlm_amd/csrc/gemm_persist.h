@@ -1,6 +1,6 @@
-// Shared pieces of the persistent 256x256 bf16 GEMM kernels (gemm_bf16_256p.hip: 8 waves, 128x64 wave tiles;
-// gemm_bf16_256q.hip: 4 waves, 128x128 wave tiles): ring geometry, activation helpers, inline-asm LDS staging
-// accessors, buffer-descriptor helpers.
+// Pieces of the persistent 256x256 bf16 GEMM kernel (gemm_bf16_256p.hip: 8 waves, 128x64 wave tiles) that its remainder-row
+// phase (gemm_strip.h) shares: ring geometry, activation helpers, inline-asm LDS staging accessors, buffer-descriptor helpers.
+// (A header because the 4-wave flavour used them too: it lost its A/B in round 2, commit b7cfcc7 last held it.)
 #pragma once
 #include "kernels.h"
 

@@ -1,5 +1,5 @@
-// Remainder rows of the persistent 256x256 bf16 GEMM kernels, computed inside the same launch (shared by
-// gemm_bf16_256p.hip and gemm_bf16_256x.hip).
+// Remainder rows of the persistent 256x256 bf16 GEMM kernel (gemm_bf16_256p.hip), computed inside the same launch.  (A header
+// because the phase-shifted "ping-pong" kernel shared it: it lost its A/B in round 3, commit b7cfcc7 last held it.)
 #pragma once
 #include "kernels.h"
 #include "gemm_persist.h"

@@ -58,9 +58,10 @@ struct GemmBf16 {
     float* splitk = nullptr;            // fp32 slab scratch for the split-K paths (few-row GEMMs); null: no split-K
     size_t splitk_bytes = 0;
     int stagger = 0;                    // persistent kernel only: odd workgroup groups start stagger x ~4 us late
-    int group_m = 4;                    // persistent kernel only: m-tiles per tile-order group (RVLM_GEMM_GROUP_M)
-    int wave_prio = 0;                  // persistent kernel only: s_setprio for waves 4-7 (RVLM_GEMM_PRIO experiment)
-    int krot = 0;                       // persistent kernel only: K-step rotation per workgroup (RVLM_GEMM_KROT experiment)
+    int group_m = 4;                    // persistent kernel only: m-tiles per tile-order group
+    int wave_prio = 0;                  // reserved argument slot, always 0: no kernel reads it
+    int krot = 0;                       // reserved argument slot, always 0.  This struct IS the kernel argument: taking the two out
+                                        // moves the code of every GEMM kernel, so they leave with the next measured change of one
     int batch_m_rows = 0;               // persistent kernel only, > 0: batched form - rows [b*batch_m_rows, ...) of A meet
                                         // rows [b*N, (b+1)*N) of Bw (the split-K weight-gradient GEMM, gemm_bf16_wgrad)
     int tn = 0;                         // persistent kernel only, 1: CONTRACTION-major operands - A = [k_rows][lda] (columns = output
@@ -68,14 +69,6 @@ struct GemmBf16 {
                                         // [b*K, (b+1)*K), rows >= k_rows read as zero (gemm_bf16_wgrad_tn)
 };
 int gemm_bf16_nt(const GemmBf16& p, hipStream_t s);
-// default routing to the phase-shifted persistent kernel (gemm_bf16_256x.hip): epilogue-kind mask and K limit, from
-// same-box A/Bs on the encoder's shapes (profiles/r03_*); RVLM_GEMM_PINGPONG / RVLM_GEMM_PINGPONG_KMAX override
-#ifndef RVLM_PINGPONG_DEFAULT_MASK
-#define RVLM_PINGPONG_DEFAULT_MASK 0
-#endif
-#ifndef RVLM_PINGPONG_DEFAULT_KMAX
-#define RVLM_PINGPONG_DEFAULT_KMAX 1024
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the last dim (eps 1e-5, biased variance), one wave per row.

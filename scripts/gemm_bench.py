@@ -13,8 +13,6 @@ shapes = [("qkv", M, 3072, 1024, 0), ("out", M, 1024, 1024, 1), ("fc1", M, 4096,
           ("fc2_dgrad", M, 4096, 1024, 3), ("fc1_dgrad", M, 1024, 4096, 0), ("cube4k", 4096, 4096, 4096, 0),
           ("cube8k", 8192, 8192, 8192, 0)]
 variants = [int(v) for v in (sys.argv[1:] or ["0", "1"])]
-if os.environ.get("GEMM_ABLATE"):
-    lib.rvlm_k_gemm_set_ablate(int(os.environ["GEMM_ABLATE"]))
 g = torch.Generator(device=dev).manual_seed(0)
 # the GPU leaves idle at a low clock and ramps up over many milliseconds: burn ~0.5 s before the first measurement
 _wa = torch.randn(8192, 8192, device=dev).bfloat16()

@@ -14,8 +14,6 @@ shapes = [("qkv", M, 3072, 1024, 0), ("out", M, 1024, 1024, 1), ("fc1", M, 4096,
           ("fc2_dgrad", M, 4096, 1024, 3), ("fc1_dgrad", M, 1024, 4096, 0), ("plain_f32", M, 1024, 1024, 4),
           ("cube8k", 8192, 8192, 8192, 0)]
 lib.rvlm_k_gemm_set_variant(int(os.environ.get("GEMM_VARIANT", "2")))
-if os.environ.get("GEMM_ABLATE"):
-    lib.rvlm_k_gemm_set_ablate(int(os.environ["GEMM_ABLATE"]))
 only = os.environ.get("TRACE_ONLY")
 if only:
     shapes = [s for s in shapes if s[0] in only.split(",")]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Step-level model of gemm_bf16_256x.hip's schedule (the persistent GEMM whose two wave groups alternate between MFMAs
-and requests + epilogue): the same programs, frontier cursor and ring-slot rules as the kernel, executed barrier by
+"""Step-level model of the phase-shifted ("ping-pong") persistent GEMM's schedule (gemm_bf16_256x.hip, whose two wave groups
+alternated between MFMAs and requests + epilogue; it lost its A/B in round 3 and commit b7cfcc7 last held it - the model stays
+as the checked statement of that schedule): the same programs, frontier cursor and ring-slot rules as the kernel, executed barrier by
 barrier for one workgroup, with every operand request and every LDS use checked:
 
   * both wave groups execute the same number of barriers (a mismatch would hang the workgroup),

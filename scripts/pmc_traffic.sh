@@ -25,7 +25,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
 rows = {k: {"launches": v["launches"], "FETCH_SIZE": round(v["FETCH_SIZE"] / max(v["launches"], 1), 1),
             "WRITE_SIZE": round(v["WRITE_SIZE"] / max(v["launches"], 1), 1)} for k, v in agg.items() if v["launches"]}
 gemm = {k: v for k, v in agg.items() if "gemm_bf16" in k or "splitk_reduce" in k}
-logical = sum(v["launches"] for k, v in gemm.items() if "256p" in k or "256q" in k or "gemm_bf16_nt_256_kernel" in k)
+logical = sum(v["launches"] for k, v in gemm.items() if "256p" in k)
 total = sum((2.0 * v["FETCH_SIZE"] + v["WRITE_SIZE"]) * 1024.0 for v in gemm.values())
 big = dict(sorted(rows.items(), key=lambda kv: -(2 * kv[1]["FETCH_SIZE"] + kv[1]["WRITE_SIZE"]) * kv[1]["launches"])[:16])
 out = {

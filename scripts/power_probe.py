@@ -43,10 +43,6 @@ def blas(): torch.matmul(A, Wt)
 fl = 2.0 * M * N * K
 run("persistent 8-wave", ours, fl)
 run("hipBLASLt (torch.matmul)", blas, fl)
-for abl, nm in ((5, "ours: MFMA only"), (1, "ours: no DMA"), (4, "ours: no LDS reads"), (2, "ours: no MFMA")):
-    lib.rvlm_k_gemm_set_ablate(abl)
-    run(nm, ours, fl)
-lib.rvlm_k_gemm_set_ablate(0)
 Z = torch.zeros_like(A); 
 def ours0(): L.check(lib.rvlm_k_gemm_bf16_nt(Z.data_ptr(), K, Z.data_ptr(), K, M, N, K, M, 0, None, out.data_ptr(), N, None, None, None, 0, L.stream_ptr()))
 run("ours, all-zero operands", ours0, fl)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B on ONE box (boxes of the pool differ by up to 5 %): the headline bench alternating between two settings.
-#   env switch:       AB_VAR=RVLM_GEMM_PINGPONG AB_VALS="0 1" bash scripts/trip_ab.sh
+#   env switch:       AB_VAR=RVLM_GEMM_TAIL AB_VALS="1 0" bash scripts/trip_ab.sh
 #   two library builds (AB_VAR=RVLM_LIB_PATH): AB_VALS="robustvlm_amd/librvlm_base.so robustvlm_amd/librvlm.so" bash scripts/trip_ab.sh
 # SKIP_TESTS=1 skips the kernel/engine parity tests in front; AB_REPS (default 2) alternations; BENCH_ARGS are passed on.
 # Output: $OUT/ab.log (one line per run: value, ms per step, GEMM roofline TFLOP/s, the twelve largest classes).

@@ -37,7 +37,7 @@ def pad_rows(t, mult=128):
     return buf
 
 
-K_128, K_256, K_PERSISTENT, K_256Q, K_SPLITK, K_STRIP = 1, 2, 4, 8, 16, 32   # include/rvlm_kernels.h RVLM_GEMM_K_*
+K_128, K_PERSISTENT, K_SPLITK, K_STRIP = 1, 4, 16, 32   # include/rvlm_kernels.h RVLM_GEMM_K_*
 
 
 def persistent_expected(M, N, K):

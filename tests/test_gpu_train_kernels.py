@@ -343,7 +343,7 @@ def transposed_arm_tiles(M, N, K):
 @pytest.mark.parametrize("M,N,K,rt", [(300, 768, 256, 6), (257 * 7, 256, 256, 30), (257 * 9, 1024, 3072, 40), (257 * 24, 1024, 1536, 100)])
 def test_reduce_partials_odd_chunk_counts_through_wgrad(M, N, K, rt):
     """Through colsum the second pass only ever sees 1, 16 or 128 partial rows (1 is covered above at every R < 256).  The transposed
-    arm of rvlm_k_wgrad_bf16 - part of the shipped library's hook (only the ENGINE's switch to it is an EXPERIMENTAL build's) - emits
+    arm of rvlm_k_wgrad_bf16 - the library's hook (rvlm_k_wgrad_set_transposed; the engine itself has no switch to that arm) - emits
     one partial row per 64-row tile: 6, 30, 40, 100.  The bias gradient per element, both accumulate modes."""
     l = lib()
     assert transposed_arm_tiles(M, N, K) == rt and rt % 16 != 0

@@ -1,4 +1,5 @@
-"""Host-side model of gemm_bf16_256x.hip's step schedule (scripts/pingpong_model.py): barrier counts of the two wave
+"""Host-side model of the ping-pong persistent GEMM's step schedule (scripts/pingpong_model.py; the kernel itself lost its A/B
+and is no longer in the tree): barrier counts of the two wave
 groups agree, every stage is requested once into a free ring slot two steps ahead and covered by a wait before it is
 read, every half tile sees K slices 0 .. nk-1 in order.  (A mismatch in the kernel would be a hang or a silent wrong
 result on the GPU; the model executes the same programs / cursor rules on the CPU.)"""
