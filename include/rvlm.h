@@ -265,24 +265,32 @@ int rvlm_project_perturbation(const float* pert, size_t n_per_sample, int B, int
 int rvlm_normalize_grad(const float* grad, size_t n_per_sample, int B, int norm_kind, float* out, rvlm_stream_t stream);
 /* One PGD step (pgd_train.py:38-63 + vlm_eval/attacks/utils.py:10,21), in place on delta/velocity:
  *   g=NaN->0; v=sign(mom*v+sign(g)); delta=clamp(delta +/- step*v, +-eps);
- *   delta=clamp(x+delta,0,1)-x.   x_adv_out (optional) = x + delta. */
+ *   delta=clamp(x+delta,0,1)-x.   x_adv_out (optional) = x + delta.
+ * It is rvlm_pgd_masked_update without a mask (one row of n elements, image_space = 1): the same kernel.  A NaN in delta, x
+ * or stepsize (or one that Inf - Inf makes of them) propagates as torch.clamp passes it on and raises RVLM_FLAG_NAN_DELTA
+ * (pgd_train.py:60). */
 int rvlm_pgd_linf_update(const float* x, const float* grad, float* delta, float* velocity,
                          size_t n, float eps, float stepsize, float momentum, int mode_max,
                          float* x_adv_out, int32_t* flags, rvlm_stream_t stream);
 /* The L2 branch of the same block (norm in [2, 'l2', ...]; vlm_eval/attacks/utils.py:12-14,22-26), per sample b over
  * its n_per_sample pixels:  g = NaN->0; g /= max(|g|_2, 1e-12); v = mom*v + g; v /= max(|v|_2, 1e-12);
  * delta +/-= step*v; delta *= eps/(|delta|_2 + 1e-7) where |delta|_2 > eps (torch.renorm); delta = clamp(x+delta,0,1)-x.
- * The norms are deterministic fp32 sums in an order of their own: equal to the reference to fp32 rounding. */
+ * The norms are deterministic fp32 sums in an order of their own: equal to the reference to fp32 rounding.
+ * The kernel of rvlm_pgd_masked_update (L2) without a mask, in its scalar walk; NaN in delta / x propagates and raises
+ * RVLM_FLAG_NAN_DELTA as in rvlm_pgd_linf_update. */
 int rvlm_pgd_l2_update(const float* x, const float* grad, float* delta, float* velocity, size_t n_per_sample, int B,
                        float eps, float stepsize, float momentum, int mode_max, float* x_adv_out, int32_t* flags,
                        rvlm_stream_t stream);
-/* One APGD step (apgd_train.py:205-229 == autopgd_base.py:328-341); step is per-sample [B]. */
+/* One APGD step (apgd_train.py:205-229 == autopgd_base.py:328-341); step is per-sample [B].  The kernel of rvlm_apgd_masked_step
+ * (L-inf) without a mask or a flag word: a NaN in x_adv, x_adv_old or step propagates as in torch.min / torch.max /
+ * torch.clamp.  16-byte accesses when n_per_sample % 4 == 0 and the pointers are 16-byte aligned; n_per_sample > 0. */
 int rvlm_apgd_linf_step(const float* x, float* x_adv, float* x_adv_old, const float* grad,
                         const float* step, float a, float eps, size_t n_per_sample, int B,
                         rvlm_stream_t stream);
 /* The L2 branch of the same step (apgd_train.py:231-254): gradient step of length `step` along grad / |grad|_2, projection
  * onto the eps ball (L2) around x and the image range, momentum mix (a, 1 - a), projection again; per-sample norms are
- * deterministic fp32 sums in an order of their own (equal to the reference to fp32 rounding). */
+ * deterministic fp32 sums in an order of their own (equal to the reference to fp32 rounding).  The kernel of rvlm_apgd_masked_step
+ * (L2) without a mask, in its scalar walk: NaN propagates through the clamps as in torch. */
 int rvlm_apgd_l2_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
                       float eps, size_t n_per_sample, int B, rvlm_stream_t stream);
 /* Per-sample APGD bookkeeping for iteration i (apgd_train.py:301-305,320-355): k and do_check

@@ -1,19 +1,11 @@
-// L-inf perturb / project / clamp kernels of the PGD and APGD loops (HBM-bound, bit-exact).
-//
-// Replaces the ~12 elementwise kernels + 4 reductions + 4 host syncs per iteration of
-// train/pgd_train.py:38-63 with ONE pass (28 B/element: read g, delta, v, x; write delta, v, x_adv)
-// and the ~25 small kernels + nonzero() syncs of train/apgd_train.py:205-229,301-355 with three.
-// Arithmetic follows SURVEY.md Appendix A exactly: one IEEE fp32 rounding per reference op, no FMA
-// contraction (this file is built with -ffp-contract=off).  NaN / range asserts become bits of a
-// device flag word that the host reads once after the loop.
-#include "common.h"
+// What the attack loops run around the step: the input range check, the standalone helpers of vlm_eval/attacks/utils.py, the APGD
+// controller and select (train/apgd_train.py:301-355 without its nonzero() syncs), the two random starts and the Square kernels.
+// The PGD update and the APGD step themselves - every caller's, masked or not - are in vlm_attack_kernels.hip.
+// Arithmetic follows SURVEY.md Appendix A exactly: one IEEE fp32 rounding per reference op, no FMA contraction (this file is
+// built with -ffp-contract=off).  NaN / range asserts become bits of a device flag word that the host reads once after the loop.
+#include "attack_common.h"
 
 namespace rvlm {
-
-__device__ __forceinline__ float sgnf(float a) {  // torch.sign: sign(+-0)=0, sign(NaN)=0
-    return (a > 0.0f) ? 1.0f : ((a < 0.0f) ? -1.0f : 0.0f);
-}
-__device__ __forceinline__ float clamp01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
 
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -25,188 +17,6 @@ check_range_kernel(const float* __restrict__ x, size_t n, int32_t* flags) {
         bad |= !(v < 1.000001f && v > -1e-6f);
     }
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags, RVLM_FLAG_INPUT_RANGE);
-}
-
-template <bool VEC>
-__global__ void __launch_bounds__(256)
-pgd_linf_update_kernel(const float* __restrict__ x, const float* __restrict__ g,
-                       float* __restrict__ delta, float* __restrict__ vel, size_t n, float eps,
-                       float step, float mom, int mode_max, float* __restrict__ x_adv_out,
-                       int32_t* flags) {
-    int f = 0;
-    constexpr int V = VEC ? 4 : 1;
-    const size_t nv = n / V;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv;
-         i += (size_t)gridDim.x * blockDim.x) {
-        float xv[V], gv[V], dv[V], vv[V], xa[V];
-        if (VEC) {
-            *(float4*)xv = ((const float4*)x)[i];
-            *(float4*)gv = ((const float4*)g)[i];
-            *(float4*)dv = ((const float4*)delta)[i];
-            *(float4*)vv = ((const float4*)vel)[i];
-        } else {
-            xv[0] = x[i]; gv[0] = g[i]; dv[0] = delta[i]; vv[0] = vel[i];
-        }
-#pragma unroll
-        for (int e = 0; e < V; ++e) {
-            float gi = gv[e];
-            if (gi != gi) { gi = 0.0f; f |= RVLM_FLAG_NAN_GRAD; }      // pgd_train.py:40-42
-            float s = sgnf(gi);                                        // utils.py:21
-            float v = sgnf(mom * vv[e] + s);                           // :46-47
-            float sv = step * v;
-            float d = mode_max ? (dv[e] + sv) : (dv[e] - sv);          // :49-52
-            d = fminf(fmaxf(d, -eps), eps);                            // :56 project_perturbation
-            float a = clamp01(xv[e] + d);
-            d = a - xv[e];                                             // :57-59
-            if (d != d) f |= RVLM_FLAG_NAN_DELTA;                      // :60
-            float s2 = xv[e] + d;                                      // :61-63 and :68
-            if (!(s2 < 1.000001f && s2 > -1e-6f)) f |= RVLM_FLAG_ADV_RANGE;
-            dv[e] = d; vv[e] = v; xa[e] = s2;
-        }
-        if (VEC) {
-            ((float4*)delta)[i] = *(float4*)dv;
-            ((float4*)vel)[i] = *(float4*)vv;
-            if (x_adv_out) ((float4*)x_adv_out)[i] = *(float4*)xa;
-        } else {
-            delta[i] = dv[0]; vel[i] = vv[0];
-            if (x_adv_out) x_adv_out[i] = xa[0];
-        }
-    }
-    if (flags) {
-        int wf = f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) wf |= __shfl_xor(wf, o, 64);
-        if (wf && (threadIdx.x & 63) == 0) atomicOr(flags, wf);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// L2 branch of pgd() (train/pgd_train.py:38-63 with vlm_eval/attacks/utils.py:12-14,22-26): the per-sample norms make
-// it three dependent reductions, so ONE workgroup owns one sample and walks its pixels four times (the sample's four
-// tensors are 2.4 MB: the later passes are L2-cache reads):
-//   g = NaN -> 0;  g /= max(|g|_2, 1e-12)                         F.normalize(grad.view(bs, -1), p=2, dim=1)
-//   v = mom * v + g;  v /= max(|v|_2, 1e-12)                      momentum, normalize again
-//   d = d +- step * v;  d *= eps / (|d|_2 + 1e-7) if |d|_2 > eps  torch.renorm(d, p=2, dim=0, maxnorm=eps)
-//   d = clamp(x + d, 0, 1) - x
-// Sums of squares are fp32 in a fixed order (lane-strided partial sums, wave shuffles, 16 wave partials in LDS):
-// deterministic, but not torch's reduction order - parity with the reference is to fp32 rounding of the norms, not
-// bit-exact like the L-inf branch.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum_1024(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();                                   // red may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += red[i];
-    return t;
-}
-
-__global__ void __launch_bounds__(1024)
-pgd_l2_update_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ delta,
-                     float* __restrict__ vel, size_t n_per, float eps, float step, float mom, int mode_max,
-                     float* __restrict__ x_adv_out, int32_t* flags) {
-    __shared__ float red[16];
-    const size_t base = (size_t)blockIdx.x * n_per;
-    const float* xs = x + base;
-    const float* gs = g + base;
-    float* ds = delta + base;
-    float* vs = vel + base;
-    int f = 0;
-    float acc = 0.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        float gi = gs[i];
-        if (gi != gi) { gi = 0.0f; f |= RVLM_FLAG_NAN_GRAD; }
-        acc = fmaf(gi, gi, acc);
-    }
-    const float gn = fmaxf(sqrtf(block_sum_1024(acc, red)), 1e-12f);
-    acc = 0.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        float gi = gs[i];
-        if (gi != gi) gi = 0.0f;
-        const float v = mom * vs[i] + gi / gn;
-        vs[i] = v;                                      // un-normalised for now (same thread re-reads it below)
-        acc = fmaf(v, v, acc);
-    }
-    const float vn = fmaxf(sqrtf(block_sum_1024(acc, red)), 1e-12f);
-    acc = 0.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        const float v = vs[i] / vn;
-        vs[i] = v;
-        const float sv = step * v;
-        const float d = mode_max ? (ds[i] + sv) : (ds[i] - sv);
-        ds[i] = d;
-        acc = fmaf(d, d, acc);
-    }
-    const float dn = sqrtf(block_sum_1024(acc, red));
-    const float sc = dn > eps ? eps / (dn + 1e-7f) : 1.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        const float xv = xs[i];
-        float d = ds[i] * sc;
-        d = clamp01(xv + d) - xv;
-        if (d != d) f |= RVLM_FLAG_NAN_DELTA;
-        const float s2 = xv + d;
-        if (!(s2 < 1.000001f && s2 > -1e-6f)) f |= RVLM_FLAG_ADV_RANGE;
-        ds[i] = d;
-        if (x_adv_out) x_adv_out[base + i] = s2;
-    }
-    if (flags) {
-        int wf = f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) wf |= __shfl_xor(wf, o, 64);
-        if (wf && (threadIdx.x & 63) == 0) atomicOr(flags, wf);
-    }
-}
-
-// L2 branch of the APGD step (train/apgd_train.py:231-254), one workgroup per sample, three per-sample norms:
-//   grad2 = x_adv - x_adv_old;  x_adv_old = x_adv
-//   z = x_adv + (step * grad) / (|grad|_2 + 1e-12)
-//   z = clamp(x + (z - x) / (|z - x|_2 + 1e-12) * min(eps, |z - x|_2), 0, 1)
-//   u = x_adv + (z - x_adv) * a + grad2 * (1 - a)
-//   x_adv = clamp(x + (u - x) / (|u - x|_2 + 1e-12) * min(eps, |u - x|_2), 0, 1)
-// z is recomputed instead of stored (x_adv and x_adv_old are rewritten only in the third pass).  fp32 sums in this
-// kernel's own fixed order: equal to the reference to fp32 rounding of the norms.
-__global__ void __launch_bounds__(1024)
-apgd_l2_step_kernel(const float* __restrict__ x, float* __restrict__ x_adv, float* __restrict__ x_adv_old,
-                    const float* __restrict__ grad, const float* __restrict__ step, float a, float one_minus_a,
-                    float eps, size_t n_per) {
-    __shared__ float red[16];
-    const size_t base = (size_t)blockIdx.x * n_per;
-    const float* xs = x + base;
-    const float* gs = grad + base;
-    float* xa = x_adv + base;
-    float* xo = x_adv_old + base;
-    const float st = step[blockIdx.x];
-    float acc = 0.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) acc = fmaf(gs[i], gs[i], acc);
-    const float gd = sqrtf(block_sum_1024(acc, red)) + 1e-12f;
-    acc = 0.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        const float z = xa[i] + (st * gs[i]) / gd;
-        const float d = z - xs[i];
-        acc = fmaf(d, d, acc);
-    }
-    const float n1 = sqrtf(block_sum_1024(acc, red));
-    const float d1 = n1 + 1e-12f, m1 = fminf(eps, n1);
-    acc = 0.0f;
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        const float xv = xs[i], av = xa[i];
-        float z = av + (st * gs[i]) / gd;
-        z = clamp01(xv + (z - xv) / d1 * m1);
-        const float g2 = av - xo[i];
-        const float u = (av + (z - av) * a) + g2 * one_minus_a;
-        xo[i] = av;
-        xa[i] = u;                                        // finished in the last pass
-        const float d = u - xv;
-        acc = fmaf(d, d, acc);
-    }
-    const float n2 = sqrtf(block_sum_1024(acc, red));
-    const float d2 = n2 + 1e-12f, m2 = fminf(eps, n2);
-    for (size_t i = threadIdx.x; i < n_per; i += 1024) {
-        const float xv = xs[i];
-        xa[i] = clamp01(xv + (xa[i] - xv) / d2 * m2);
-    }
 }
 
 // ---- the standalone helpers of vlm_eval/attacks/utils.py:8-26 as device kernels (robustvlm_amd/attack_utils.py) ----
@@ -237,32 +47,6 @@ row_l2_scale_kernel(const float* __restrict__ x, size_t n_per, int mode, float m
     } else {
         const float sc = nrm > maxnorm ? maxnorm / (nrm + 1e-7f) : 1.0f;
         for (size_t i = threadIdx.x; i < n_per; i += 1024) out[base + i] = x[base + i] * sc;
-    }
-}
-
-// one block row per sample chunk: blockIdx.y = sample
-__global__ void __launch_bounds__(256)
-apgd_linf_step_kernel(const float* __restrict__ x, float* __restrict__ x_adv,
-                      float* __restrict__ x_adv_old, const float* __restrict__ grad,
-                      const float* __restrict__ step, float a, float one_minus_a, float eps,
-                      size_t n_per) {
-    const int b = blockIdx.y;
-    const float st = step[b];
-    const size_t base = (size_t)b * n_per;
-    for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_per;
-         j += (size_t)gridDim.x * blockDim.x) {
-        size_t i = base + j;
-        float xa = x_adv[i], xo = x_adv_old[i], xc = x[i];
-        float grad2 = xa - xo;                                   // apgd_train.py:206
-        float lo = xc - eps, hi = xc + eps;
-        float z = xa + st * sgnf(grad[i]);                       // :213
-        z = clamp01(fminf(fmaxf(z, lo), hi));                    // :214-221
-        float t1 = (z - xa) * a;
-        float t2 = grad2 * one_minus_a;
-        float u = (xa + t1) + t2;                                // :225
-        u = clamp01(fminf(fmaxf(u, lo), hi));                    // :222-229
-        x_adv_old[i] = xa;                                       // :207
-        x_adv[i] = u;
     }
 }
 
@@ -362,13 +146,6 @@ l2_random_start_kernel(const float* __restrict__ x, const float* __restrict__ t,
     for (size_t j = threadIdx.x; j < n_per; j += 1024) x_adv[base + j] = x[base + j] + eps * (t[base + j] / den);
 }
 
-static inline int ew_grid(size_t n, int per_thread = 4) {
-    size_t blocks = (n / per_thread + 255) / 256;
-    if (blocks < 1) blocks = 1;
-    if (blocks > 256 * 8) blocks = 256 * 8;  // 256 CUs x 8 blocks, grid-stride the rest
-    return (int)blocks;
-}
-
 }  // namespace rvlm
 
 using namespace rvlm;
@@ -413,49 +190,6 @@ extern "C" int rvlm_check_image_range(const float* x, size_t n, int32_t* flags,
     return RVLM_OK;
 }
 
-extern "C" int rvlm_pgd_linf_update(const float* x, const float* grad, float* delta,
-                                    float* velocity, size_t n, float eps, float stepsize,
-                                    float momentum, int mode_max, float* x_adv_out, int32_t* flags,
-                                    rvlm_stream_t stream) {
-    RVLM_REQUIRE(x && grad && delta && velocity, "rvlm_pgd_linf_update: null pointer");
-    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    bool vec = (n % 4 == 0) && al(x) && al(grad) && al(delta) && al(velocity) &&
-               (!x_adv_out || al(x_adv_out));
-    if (vec)
-        hipLaunchKernelGGL(pgd_linf_update_kernel<true>, dim3(ew_grid(n, 4)), dim3(256), 0,
-                           (hipStream_t)stream, x, grad, delta, velocity, n, eps, stepsize,
-                           momentum, mode_max, x_adv_out, flags);
-    else
-        hipLaunchKernelGGL(pgd_linf_update_kernel<false>, dim3(ew_grid(n, 1)), dim3(256), 0,
-                           (hipStream_t)stream, x, grad, delta, velocity, n, eps, stepsize,
-                           momentum, mode_max, x_adv_out, flags);
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
-}
-
-extern "C" int rvlm_pgd_l2_update(const float* x, const float* grad, float* delta, float* velocity, size_t n_per_sample,
-                                  int B, float eps, float stepsize, float momentum, int mode_max, float* x_adv_out,
-                                  int32_t* flags, rvlm_stream_t stream) {
-    RVLM_REQUIRE(x && grad && delta && velocity && n_per_sample > 0 && B > 0, "rvlm_pgd_l2_update: bad arguments");
-    hipLaunchKernelGGL(pgd_l2_update_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, grad, delta, velocity,
-                       n_per_sample, eps, stepsize, momentum, mode_max, x_adv_out, flags);
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
-}
-
-extern "C" int rvlm_apgd_linf_step(const float* x, float* x_adv, float* x_adv_old,
-                                   const float* grad, const float* step, float a, float eps,
-                                   size_t n_per_sample, int B, rvlm_stream_t stream) {
-    RVLM_REQUIRE(x && x_adv && x_adv_old && grad && step && B > 0, "rvlm_apgd_linf_step: bad args");
-    int gx = (int)((n_per_sample + 1023) / 1024);
-    if (gx > 64) gx = 64;
-    float oma = (float)(1.0 - (double)a);
-    hipLaunchKernelGGL(apgd_linf_step_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, x,
-                       x_adv, x_adv_old, grad, step, a, oma, eps, n_per_sample);
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
-}
-
 extern "C" int rvlm_project_perturbation(const float* pert, size_t n_per_sample, int B, int norm_kind, float eps, float* out,
                                          rvlm_stream_t stream) {
     RVLM_REQUIRE(pert && out && B > 0 && n_per_sample > 0, "rvlm_project_perturbation: bad arguments");
@@ -479,16 +213,6 @@ extern "C" int rvlm_normalize_grad(const float* grad, size_t n_per_sample, int B
         hipLaunchKernelGGL(row_l2_scale_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, grad, n_per_sample, 0, 0.0f, out);
     else
         return fail(RVLM_ERR_UNSUPPORTED, "rvlm_normalize_grad: norm must be L-inf (0) or L2 (2)");
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
-}
-
-extern "C" int rvlm_apgd_l2_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step,
-                                 float a, float eps, size_t n_per_sample, int B, rvlm_stream_t stream) {
-    RVLM_REQUIRE(x && x_adv && x_adv_old && grad && step && B > 0 && n_per_sample > 0, "rvlm_apgd_l2_step: bad args");
-    const float oma = (float)(1.0 - (double)a);
-    hipLaunchKernelGGL(apgd_l2_step_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, x_adv, x_adv_old, grad, step,
-                       a, oma, eps, n_per_sample);
     RVLM_CHECK_LAUNCH();
     return RVLM_OK;
 }

@@ -1,4 +1,7 @@
-// Masked PGD / APGD kernels of the VLM-side attacks (vlm_eval/attacks/pgd.py, apgd.py; RVLM_HAS_VLM_ATTACKS).
+// The PGD update and the APGD step, L-inf and L2, for every caller: the pooled-embedding attacks (train/pgd_train.py:38-63,
+// train/apgd_train.py:205-254; rvlm_pgd_linf_update, rvlm_pgd_l2_update, rvlm_apgd_linf_step, rvlm_apgd_l2_step) and the masked
+// VLM-side attacks (vlm_eval/attacks/pgd.py, apgd.py; RVLM_HAS_VLM_ATTACKS).  One kernel per formula: the pooled entries are its
+// mask-less case, mask == NULL and n_img == 1.
 //
 // The attacked tensor is [B, n_img, P] fp32 (P = elements of one image: the reference's [B, n_img, 1, 3, H, W] with everything
 // behind axis 1 flattened) and the reference's full-size 0/1 mask is constant behind axis 1, so it travels as uint8 mask[n_img]
@@ -6,9 +9,9 @@
 //   PGD.perturb  pgd.py:39-65   -> rvlm_pgd_masked_update                        (1 launch; the reference: ~20 + 2 host asserts)
 //   apgd         apgd.py:240-266 -> rvlm_apgd_masked_step                        (1 launch)
 //                apgd.py:321-351 -> rvlm_apgd_masked_bookkeeping                 (2 launches, no nonzero() read-back)
-// Arithmetic: one IEEE fp32 rounding per reference op in the reference's order, no contraction (-ffp-contract=off), the same
-// per-element sequences as the pooled-embedding kernels of attack_kernels.hip with two differences: the mask, and clamps that
-// propagate NaN like torch.clamp / torch.min / torch.max do (so a NaN reaches the flag the reference's assert stands for).
+// Arithmetic: SURVEY.md Appendix A - one IEEE fp32 rounding per reference op in the reference's order, no contraction
+// (-ffp-contract=off).  Clamps propagate NaN like torch.clamp / torch.min / torch.max do (so a NaN reaches the flag the reference's
+// assert stands for); NaN / range asserts become bits of a device flag word that the host reads once after the loop.
 // A masked gradient is `g * 0` as in the reference, not a skipped element: NaN / Inf under a 0 of the mask becomes NaN there too.
 //
 // Masked images and bit-identity.  The reference never skips a masked image, it steps it along a zero gradient and projects it
@@ -20,18 +23,15 @@
 //
 // L-inf kernels: blockIdx.y = b * n_img + image, the mask byte is uniform per workgroup, 16-byte accesses when P % 4 == 0 and
 // every pointer is 16-byte aligned, the scalar instantiation otherwise (image bases are then not 16-byte aligned).  L2 kernels:
-// one workgroup of 1024 threads owns one sample and walks it once per dependent norm, as pgd_l2_update_kernel does (the later
-// walks are L2-cache reads); sums are fp32 in a fixed order - lane partials over (image, element) in ascending order, wave
-// shuffles, 16 wave partials in LDS added in wave order - so results are bit-reproducible run to run, equal to torch's to fp32
-// rounding of the norms.  The only atomic is the OR into the flags word, whose value does not depend on order.
-#include "common.h"
+// one workgroup of 1024 threads owns one sample and walks it once per dependent norm (the later walks are L2-cache reads: the
+// four tensors of a 3 x 224 x 224 sample are 2.4 MB); sums are fp32 in a fixed order - lane partials over (image, element) in
+// ascending order, wave shuffles, 16 wave partials in LDS added in wave order - so results are bit-reproducible run to run, equal
+// to torch's to fp32 rounding of the norms.  The only atomic is the OR into the flags word, whose value does not depend on order.
+#include "attack_common.h"
 
 namespace rvlm {
 namespace {
 
-__device__ __forceinline__ float sgnf(float a) {  // torch.sign: sign(+-0) = 0, sign(NaN) = 0
-    return (a > 0.0f) ? 1.0f : ((a < 0.0f) ? -1.0f : 0.0f);
-}
 // torch.clamp / torch.min / torch.max return NaN for a NaN operand (fminf / fmaxf would drop it)
 __device__ __forceinline__ float clampn(float v, float lo, float hi) { return (v != v) ? v : fminf(fmaxf(v, lo), hi); }
 __device__ __forceinline__ float maskg(float g, bool on) { return on ? g : g * 0.0f; }   // mask * gradient
@@ -48,16 +48,6 @@ __device__ __forceinline__ void raise_flags(int32_t* flags, int f) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) f |= __shfl_xor(f, o, 64);
     if (f && (threadIdx.x & 63) == 0) atomicOr(flags, f);
-}
-__device__ __forceinline__ float block_sum_1024(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();                                   // red may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) t += red[i];
-    return t;
 }
 // one sample [n_img, P] by a workgroup of 1024 threads: f(offset in the sample, image attacked?) on V consecutive elements
 template <int V, typename F>
@@ -400,6 +390,60 @@ extern "C" int rvlm_apgd_masked_step(const float* x, float* x_adv, float* x_adv_
             hipLaunchKernelGGL(apgd_masked_l2_kernel<1>, dim3(B), dim3(1024), 0, (hipStream_t)stream, RVLM_APGD_MASKED_ARGS);
     }
 #undef RVLM_APGD_MASKED_ARGS
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+
+// ---- the pooled-embedding entries: the same kernels without a mask, one image per sample --------------------------------------
+extern "C" int rvlm_pgd_linf_update(const float* x, const float* grad, float* delta, float* velocity, size_t n, float eps,
+                                    float stepsize, float momentum, int mode_max, float* x_adv_out, int32_t* flags,
+                                    rvlm_stream_t stream) {
+    RVLM_REQUIRE(x && grad && delta && velocity, "rvlm_pgd_linf_update: null pointer");
+    // elementwise over the whole batch: ONE row of n elements on the flat grid (image_grid's 64 workgroups per row would leave
+    // three quarters of the CUs idle at a batch's 19 M elements)
+    if (n % 4 == 0 && aligned16({x, grad, delta, velocity, x_adv_out}))
+        hipLaunchKernelGGL(pgd_masked_linf_kernel<4>, dim3(ew_grid(n, 4)), dim3(256), 0, (hipStream_t)stream, x, grad, delta,
+                           velocity, nullptr, 1, n, eps, stepsize, momentum, mode_max, 1, x_adv_out, flags);
+    else
+        hipLaunchKernelGGL(pgd_masked_linf_kernel<1>, dim3(ew_grid(n, 1)), dim3(256), 0, (hipStream_t)stream, x, grad, delta,
+                           velocity, nullptr, 1, n, eps, stepsize, momentum, mode_max, 1, x_adv_out, flags);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+
+// The two pooled L2 entries always take the scalar walk, V = 1: lane t sums elements t, t + 1024, ... - the order their norms
+// have always had, so their outputs keep their bits.  The 16-byte walk would be faster and would change the last bits of every
+// norm: a change of its own.
+extern "C" int rvlm_pgd_l2_update(const float* x, const float* grad, float* delta, float* velocity, size_t n_per_sample, int B,
+                                  float eps, float stepsize, float momentum, int mode_max, float* x_adv_out, int32_t* flags,
+                                  rvlm_stream_t stream) {
+    RVLM_REQUIRE(x && grad && delta && velocity && n_per_sample > 0 && B > 0, "rvlm_pgd_l2_update: bad arguments");
+    hipLaunchKernelGGL(pgd_masked_l2_kernel<1>, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, grad, delta, velocity, nullptr, 1,
+                       n_per_sample, eps, stepsize, momentum, mode_max, 1, x_adv_out, flags);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+
+extern "C" int rvlm_apgd_l2_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
+                                 float eps, size_t n_per_sample, int B, rvlm_stream_t stream) {
+    RVLM_REQUIRE(x && x_adv && x_adv_old && grad && step && B > 0 && n_per_sample > 0, "rvlm_apgd_l2_step: bad args");
+    const float oma = (float)(1.0 - (double)a);
+    hipLaunchKernelGGL(apgd_masked_l2_kernel<1>, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, x_adv, x_adv_old, grad, nullptr,
+                       step, a, oma, eps, 1, n_per_sample, nullptr);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+
+extern "C" int rvlm_apgd_linf_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
+                                   float eps, size_t n_per_sample, int B, rvlm_stream_t stream) {
+    RVLM_REQUIRE(x && x_adv && x_adv_old && grad && step && B > 0 && n_per_sample > 0, "rvlm_apgd_linf_step: bad args");
+    const float oma = (float)(1.0 - (double)a);
+    if (n_per_sample % 4 == 0 && aligned16({x, x_adv, x_adv_old, grad}))
+        hipLaunchKernelGGL(apgd_masked_linf_kernel<4>, image_grid(n_per_sample, 4, B), dim3(256), 0, (hipStream_t)stream, x, x_adv,
+                           x_adv_old, grad, nullptr, step, a, oma, eps, 1, n_per_sample, nullptr);
+    else
+        hipLaunchKernelGGL(apgd_masked_linf_kernel<1>, image_grid(n_per_sample, 1, B), dim3(256), 0, (hipStream_t)stream, x, x_adv,
+                           x_adv_old, grad, nullptr, step, a, oma, eps, 1, n_per_sample, nullptr);
     RVLM_CHECK_LAUNCH();
     return RVLM_OK;
 }

@@ -493,3 +493,134 @@ def test_apgd_train_ignores_a_rho_left_on_the_handle():
     assert torch.equal(run(), want)
     L.check(eng.lib.rvlm_vit_set_apgd_rho(eng._h, C.c_double(0.75)))
     eng.close()
+
+
+# ------------------------------------------------------------------ NaN in the attacked tensor propagates as in torch
+def _nan_and_bits(got, want, name, bits=True, atol=0.0):
+    """NaN exactly where torch has it; elsewhere the same bits (bits) or within atol."""
+    assert torch.equal(got.isnan(), want.isnan()), (name, got.isnan().nonzero().tolist(), want.isnan().nonzero().tolist())
+    ok = ~want.isnan()
+    if bits:
+        assert torch.equal(got[ok].view(torch.int32), want[ok].view(torch.int32)), name
+    else:
+        assert float((got[ok] - want[ok]).abs().max()) <= atol, name
+
+
+def _l2n(t):
+    return (t ** 2).sum(dim=1, keepdim=True).sqrt()
+
+
+@pytest.mark.parametrize("P", [8, 7])
+def test_step_entries_propagate_nan_like_torch(P):
+    """A NaN in delta (PGD) or x_adv (APGD) comes out as NaN exactly where the same update written with torch ops has it
+    (torch.clamp / torch.min / torch.max propagate NaN; pgd_train.py:60 asserts on it), the PGD entries raise FLAG_NAN_DELTA,
+    and the other sample of the batch does not notice: it equals its result when run alone, bit for bit.  B = 2 samples of
+    P = 8 (16-byte accesses) and P = 7 (scalar) elements; sample 0 holds NaN at two positions.  L-inf outputs equal torch's
+    bits at the finite positions; the L2 outputs equal torch to fp32 rounding of the per-sample norms (2e-6 absolute on
+    values in [0,1], the tolerance of the L2 golden tests above)."""
+    l = lib()
+    B, nan_at = 2, (1, 5)
+    eps, stepsize, mom, a = float(F32(8 / 255)), float(F32(2 / 255)), float(F32(0.9)), 0.75
+    g = torch.Generator().manual_seed(11 + P)
+    x = torch.rand(B, P, generator=g).to(dev())
+    grad = torch.randn(B, P, generator=g).to(dev())
+    delta0 = ((torch.rand(B, P, generator=g) * 2 - 1) * eps).to(dev())
+    vel0 = torch.randn(B, P, generator=g).sign().to(dev())
+    xadv0 = (x + delta0).clamp(0, 1)
+    xold0 = (x + ((torch.rand(B, P, generator=g) * 2 - 1) * eps).to(dev())).clamp(0, 1)
+    step = torch.tensor([[float(F32(2 * eps))], [float(F32(eps / 2))]], device=dev())
+    for j in nan_at:
+        delta0[0, j] = float("nan")
+        xadv0[0, j] = float("nan")
+
+    # ---- PGD update, mode 'max' (pgd_train.py:38-63, vlm_eval/attacks/utils.py:8-26)
+    def pgd_torch(norm):
+        gr = grad.clone()
+        gr[gr.isnan()] = 0.0
+        if norm == "linf":
+            v = (mom * vel0 + gr.sign()).sign()
+            d = torch.clamp(delta0 + stepsize * v, -eps, eps)
+        else:
+            v = torch.nn.functional.normalize(mom * vel0 + torch.nn.functional.normalize(gr, p=2, dim=1), p=2, dim=1)
+            d = torch.renorm(delta0 + stepsize * v, p=2, dim=0, maxnorm=eps)
+        d = torch.clamp(x + d, 0, 1) - x
+        return d, v, x + d
+
+    def pgd_hip(norm, rows):
+        xs, gs = x[rows].clone(), grad[rows].clone()
+        d, v, xa = delta0[rows].clone(), vel0[rows].clone(), torch.zeros_like(xs)
+        flags = torch.zeros(1, dtype=torch.int32, device=dev())
+        if norm == "linf":
+            L.check(l.rvlm_pgd_linf_update(xs.data_ptr(), gs.data_ptr(), d.data_ptr(), v.data_ptr(), xs.numel(), eps, stepsize,
+                                           mom, 1, xa.data_ptr(), flags.data_ptr(), st()))
+        else:
+            L.check(l.rvlm_pgd_l2_update(xs.data_ptr(), gs.data_ptr(), d.data_ptr(), v.data_ptr(), P, xs.shape[0], eps, stepsize,
+                                         mom, 1, xa.data_ptr(), flags.data_ptr(), st()))
+        torch.cuda.synchronize()
+        return (d, v, xa), int(flags.item())
+
+    for norm in ("linf", "l2"):
+        want = pgd_torch(norm)
+        got, fl = pgd_hip(norm, slice(0, 2))
+        for name, gt, wt in zip(("delta", "velocity", "x_adv"), got, want):
+            assert int(wt[0].isnan().sum()) == (0 if name == "velocity" else len(nan_at)) and not wt[1].isnan().any()
+            _nan_and_bits(gt, wt, f"pgd {norm} {name}", bits=norm == "linf", atol=2e-6)
+        assert fl & L.FLAG_NAN_DELTA, (norm, fl)
+        alone, fl1 = pgd_hip(norm, slice(1, 2))
+        assert not fl1 & L.FLAG_NAN_DELTA
+        for name, gt, al in zip(("delta", "velocity", "x_adv"), got, alone):
+            assert torch.equal(gt[1:2].view(torch.int32), al.view(torch.int32)), f"pgd {norm} {name}: sample 1 alone"
+
+    # ---- APGD step, a = 0.75 (apgd_train.py:205-254)
+    def apgd_torch(norm):
+        grad2 = xadv0 - xold0
+        if norm == "linf":
+            z = xadv0 + step * grad.sign()
+            z = torch.clamp(torch.min(torch.max(z, x - eps), x + eps), 0.0, 1.0)
+            u = torch.clamp(torch.min(torch.max(xadv0 + (z - xadv0) * a + grad2 * (1 - a), x - eps), x + eps), 0.0, 1.0)
+        else:
+            z = xadv0 + step * grad / (_l2n(grad) + 1e-12)
+            z = torch.clamp(x + (z - x) / (_l2n(z - x) + 1e-12) * torch.min(eps * torch.ones_like(x), _l2n(z - x)), 0.0, 1.0)
+            u = xadv0 + (z - xadv0) * a + grad2 * (1 - a)
+            u = torch.clamp(x + (u - x) / (_l2n(u - x) + 1e-12) * torch.min(eps * torch.ones_like(x), _l2n(u - x)), 0.0, 1.0)
+        return u, xadv0.clone()
+
+    def apgd_hip(norm, rows):
+        xs, gs, ss = x[rows].clone(), grad[rows].clone(), step[rows].clone()
+        xa, xo = xadv0[rows].clone(), xold0[rows].clone()
+        fn = l.rvlm_apgd_linf_step if norm == "linf" else l.rvlm_apgd_l2_step
+        L.check(fn(xs.data_ptr(), xa.data_ptr(), xo.data_ptr(), gs.data_ptr(), ss.data_ptr(), a, eps, P, xs.shape[0], st()))
+        torch.cuda.synchronize()
+        return xa, xo
+
+    for norm in ("linf", "l2"):
+        want = apgd_torch(norm)
+        got = apgd_hip(norm, slice(0, 2))
+        assert want[0][0].isnan().any() and not want[0][1].isnan().any()
+        _nan_and_bits(got[0], want[0], f"apgd {norm} x_adv", bits=norm == "linf", atol=2e-6)
+        _nan_and_bits(got[1], want[1], f"apgd {norm} x_adv_old")
+        alone = apgd_hip(norm, slice(1, 2))
+        for name, gt, al in zip(("x_adv", "x_adv_old"), got, alone):
+            assert torch.equal(gt[1:2].view(torch.int32), al.view(torch.int32)), f"apgd {norm} {name}: sample 1 alone"
+
+
+@pytest.mark.parametrize("P", [150528, 150528 + 1])
+def test_apgd_linf_step_vs_c_oracle_image_size(P):
+    """rvlm_apgd_linf_step at one 3 x 224 x 224 image per sample, where the 64 workgroups of a sample's grid row take several
+    trips of the grid-stride loop (16-byte accesses), and at one element more (scalar accesses, sample bases off 16 bytes):
+    two steps, a = 1 then 0.75, bit for bit against the C oracle."""
+    l = lib()
+    rng = np.random.default_rng(P)
+    B, eps = 2, 4 / 255
+    x = rng.random((B, P), dtype=F32)
+    x_adv = np.clip(x + rng.uniform(-eps, eps, (B, P)).astype(F32), 0, 1).astype(F32)
+    x_old = np.clip(x + rng.uniform(-eps, eps, (B, P)).astype(F32), 0, 1).astype(F32)
+    grad = rng.standard_normal((B, P)).astype(F32)
+    grad[rng.random((B, P)) < 0.1] = 0.0
+    step = np.array([2 * eps, eps / 2], dtype=F32)
+    dx, da, do, dg, ds = _cu(x), _cu(x_adv), _cu(x_old), _cu(grad), _cu(step)
+    for a in (1.0, 0.75):
+        linf_c.apgd_linf_step(x, x_adv, x_old, grad, step, a, eps)
+        L.check(l.rvlm_apgd_linf_step(dx.data_ptr(), da.data_ptr(), do.data_ptr(), dg.data_ptr(), ds.data_ptr(), a, eps, P, B, st()))
+        torch.cuda.synchronize()
+        assert np.array_equal(da.cpu().numpy(), x_adv) and np.array_equal(do.cpu().numpy(), x_old), a
