@@ -41,6 +41,8 @@ extern "C" {
 /* RVLM_HAS_VLM_ATTACKS: the per-iteration kernels of vlm_eval/attacks/pgd.py / apgd.py on a [B, n_img, P] tensor with a per-image
  * mask - rvlm_mask_grad, rvlm_pgd_masked_update, rvlm_apgd_masked_step, rvlm_apgd_masked_bookkeeping */
 #define RVLM_HAS_VLM_ATTACKS 1
+/* RVLM_HAS_SQUARE_L2: rvlm_square_l2_propose (one query of the L2 Square Attack) and RVLM_FLAG_SQUARE_NONFINITE */
+#define RVLM_HAS_SQUARE_L2 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -76,7 +78,9 @@ enum {
     /* rvlm_fab_projection_linf / rvlm_fab_linf_step (RVLM_HAS_FAB) */
     RVLM_FLAG_FAB_NONFINITE = 64, /* NaN / Inf in a row's w, t or b: that row gets lambda = 0 (no move) */
     /* rvlm_tokens_l2_loss_grad and the loops built on it (RVLM_HAS_TOKENS) */
-    RVLM_FLAG_TOKENS_NONFINITE = 128 /* NaN / Inf in an image's token loss (its tokens or their reference) */
+    RVLM_FLAG_TOKENS_NONFINITE = 128, /* NaN / Inf in an image's token loss (its tokens or their reference) */
+    /* rvlm_square_l2_propose (RVLM_HAS_SQUARE_L2) */
+    RVLM_FLAG_SQUARE_NONFINITE = 256 /* NaN / Inf in a candidate (square.py:416-417): that row of x_new = x_best */
 };
 
 /* ---------------------------------------------------------------------------------------------
@@ -329,6 +333,21 @@ int rvlm_square_linf_propose(const float* x, const float* x_best, const int64_t*
 /* square.py:288-291: x_best[idx[a]] = x_new[a] for the candidates with take[a] != 0 (loss improved or misclassified). */
 int rvlm_square_accept(float* x_best, const float* x_new, const int64_t* idx, const float* take, int n_active,
                        size_t n_per_image, rvlm_stream_t stream);
+/* Square Attack, L2 (RVLM_HAS_SQUARE_L2): one query of the L2 branch of SquareAttack.attack_single_run (autoattack/square.py:339-379)
+ * in one launch, for the n_active still-robust images idx[a], written compactly to x_new [n_active, C, H, W] as above.  With
+ * delta = x_best - x, window 1 = rows [vh, vh+s) x columns [vw, vw+s) and window 2 the same at (vh2, vw2), per image and channel c:
+ *   new = eta * sign[a, c] + delta[win1] / (1e-12 + |delta[win1]|_c)
+ *   new = new / (1e-12 + |new|_c) * sqrt(max(eps^2 - |delta|^2, 0) / C + |delta[win1 u win2]|_c^2)
+ *   delta[win2] = 0, then delta[win1] = new;   x_new = clamp(x + eps * delta / (|delta| + 1e-12), 0, 1)
+ * eta: [s, s] floats (the reference's eta(s), already transposed if its coin said so); sign: [n_active, C] floats.  delta and the
+ * windows are never stored.  Every norm is a deterministic fp32 sum in the kernel's own fixed order (no atomics): the same bits on
+ * every run, not the bits of torch's sum.  flags (optional device word) |= RVLM_FLAG_SQUARE_NONFINITE for an image whose sums hold
+ * NaN / Inf (the reference's asserts, :416-417); its row of x_new is x_best.  Both windows must lie inside the image, eps finite and
+ * > 0 (RVLM_ERR_ARG); C <= 16 (RVLM_ERR_UNSUPPORTED).  16-byte accesses when W % 4 == 0 and the pointers are 16-byte aligned, a scalar
+ * path otherwise.  rvlm_square_accept is the accept step of both norms. */
+int rvlm_square_l2_propose(const float* x, const float* x_best, const int64_t* idx, int n_active, int C, int H, int W, int vh,
+                           int vw, int vh2, int vw2, int s, float eps, const float* eta, const float* sign, float* x_new,
+                           int32_t* flags, rvlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * FAB / FAB-T, L-inf (RVLM_HAS_FAB): the device arithmetic of one iteration of FABAttack.attack_single_run
@@ -632,7 +651,8 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * rvlm_fab_* (FAB / FAB-T L-inf), RVLM_LOSS_LOGIT_DIFF, RVLM_FLAG_FAB_NONFINITE (announced by RVLM_HAS_FAB);
                            * rvlm_vit_set_input_size, rvlm_resize_bicubic(_adjoint), rvlm_resize_taps (announced by RVLM_HAS_INPUT_RESIZE);
                            * rvlm_vit_forward_tokens, rvlm_vit_backward_input_tokens, rvlm_tokens_l2_loss_grad, rvlm_vit_tokens_fwd_inputgrad,
-                           * rvlm_pgd_run_tokens, RVLM_FLAG_TOKENS_NONFINITE (announced by RVLM_HAS_TOKENS) */
+                           * rvlm_pgd_run_tokens, RVLM_FLAG_TOKENS_NONFINITE (announced by RVLM_HAS_TOKENS);
+                           * rvlm_square_l2_propose, RVLM_FLAG_SQUARE_NONFINITE (announced by RVLM_HAS_SQUARE_L2) */
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ FLAG_INPUT_RANGE, FLAG_NAN_GRAD, FLAG_NAN_DELTA, FLAG_ADV_RANGE = 1, 2, 4, 8
 FLAG_TOKEN_RANGE, FLAG_EOT_ACTIVE = 16, 32
 FLAG_FAB_NONFINITE = 64
 FLAG_TOKENS_NONFINITE = 128
+FLAG_SQUARE_NONFINITE = 256
 TOKENS_ALL, TOKENS_PATCH = 0, 1
 
 c_f32p = C.c_void_p   # device pointers travel as integers (tensor.data_ptr())
@@ -308,6 +309,11 @@ _SIGS.update({
     "rvlm_k_pos_cls_grad": (C.c_int, [c_f32p, C.c_long, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_stream]),
     "rvlm_k_gather_patch_rows": (C.c_int, [c_f32p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, c_stream]),
     "rvlm_k_transpose_pad": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_int, c_stream]),
+})
+_SIGS.update({
+    # Square Attack, L2: one query in one launch (csrc/attack_kernels.hip; RVLM_HAS_SQUARE_L2)
+    "rvlm_square_l2_propose": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, C.c_void_p, c_stream]),
 })
 EXPORTED_SYMBOLS = tuple(_SIGS)
 

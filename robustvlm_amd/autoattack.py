@@ -6,12 +6,14 @@ iterations_apgd=..., use_rs=...)`` then ``run_standard_evaluation(x, y, bs=...)`
 native :class:`~robustvlm_amd.autopgd.APGDAttack` / :class:`~robustvlm_amd.autopgd.APGDAttack_targeted` (whole loops on
 the device when ``model`` is a :class:`~robustvlm_amd.clip_model.ClassificationModel` over the engine).
 
-Built: ``apgd-ce``, ``apgd-dlr``, ``apgd-t``, ``square`` (the black-box route of clip_robustbench.py:150-151, L-inf;
-:class:`~robustvlm_amd.square.SquareAttack`) and ``fab`` / ``fab-t`` (L-inf; :class:`~robustvlm_amd.fab.FABAttack`), so
-``version='standard'`` and ``'plus'`` run end to end for ``norm='Linf'``.  Square and FAB have no L2 / L1 form and FAB has
-no CPU path: where they cannot run (another norm, an attack device or inputs that are not a GPU) the pre-flight check of
-``run_standard_evaluation`` raises NotImplementedError before any attack time is spent; their hyper-parameter holder
-exists in every case so that ``set_version`` and user code that tweaks ``adversary.fab.n_restarts`` keep working.
+Built: ``apgd-ce``, ``apgd-dlr``, ``apgd-t``, ``square`` (the black-box route of clip_robustbench.py:150-151, L-inf and
+L2; :class:`~robustvlm_amd.square.SquareAttack`) and ``fab`` / ``fab-t`` (L-inf; :class:`~robustvlm_amd.fab.FABAttack`), so
+``version='standard'`` and ``'plus'`` run end to end for ``norm='Linf'``, and ``norm='L2'`` runs the custom lists over
+``apgd-ce`` / ``apgd-dlr`` / ``apgd-t`` / ``square``.  ``version='standard'`` with ``norm='L2'`` still refuses, because of
+``fab-t``: FAB has no L2 / L1 form, Square has no L1 form, and FAB has no CPU path.  Where an attack cannot run (another
+norm, an attack device or inputs that are not a GPU) the pre-flight check of ``run_standard_evaluation`` raises
+NotImplementedError before any attack time is spent; the hyper-parameter holder of such an attack exists in every case so
+that ``set_version`` and user code that tweaks ``adversary.fab.n_restarts`` keep working.
 """
 from __future__ import annotations
 
@@ -136,13 +138,13 @@ class AutoAttack():
                       device=device, logger=self.logger, alpha=alpha, use_rs=use_rs)
         self.apgd = APGDAttack(model, n_restarts=5, **common)                       # autoattack.py:34-36
         self.apgd_targeted = APGDAttack_targeted(model, n_restarts=1, **common)     # :47-49
-        # L-inf only attacks; otherwise hyper-parameter holders (see module docstring)
+        # FAB is L-inf only, Square L-inf / L2; otherwise hyper-parameter holders (see module docstring)
         if norm == 'Linf':                                                          # autoattack.py:38-40
             self.fab = FABAttack(model, n_restarts=5, n_iter=100, eps=eps, seed=seed, norm=norm, verbose=False,
                                  device=device)
         else:
             self.fab = SimpleNamespace(n_restarts=5, n_iter=100, n_target_classes=9, targeted=False, seed=seed)
-        if norm == 'Linf':                                                          # autoattack.py:42-44
+        if norm in ('Linf', 'L2'):                                                  # autoattack.py:42-44
             self.square = SquareAttack(model, p_init=.8, n_queries=5000, eps=eps, norm=norm, n_restarts=1, seed=seed,
                                        verbose=False, device=device, resc_schedule=False)
         else:
@@ -232,10 +234,10 @@ class AutoAttack():
         raise ValueError('Attack not supported')
 
     def _unavailable(self, attack):
-        """Why a known attack cannot run in this configuration ('' if it can): Square and FAB are L-inf only, FAB has no
-        CPU path (its projection and bookkeeping are HIP kernels)."""
+        """Why a known attack cannot run in this configuration ('' if it can): FAB is L-inf only, Square L-inf / L2, FAB has
+        no CPU path (its projection and bookkeeping are HIP kernels)."""
         if attack == 'square' and not isinstance(self.square, SquareAttack):
-            return f"square is built for norm='Linf' only (norm={self.norm!r})"
+            return f"square is built for norm='Linf' and 'L2' only (norm={self.norm!r})"
         if attack in ('fab', 'fab-t'):
             if not isinstance(self.fab, FABAttack):
                 return f"{attack} is built for norm='Linf' only (norm={self.norm!r})"

@@ -1,5 +1,5 @@
 // What the attack loops run around the step: the input range check, the standalone helpers of vlm_eval/attacks/utils.py, the APGD
-// controller and select (train/apgd_train.py:301-355 without its nonzero() syncs), the two random starts and the Square kernels.
+// controller and select (train/apgd_train.py:301-355 without its nonzero() syncs), the two random starts and the Square kernels (L-inf and L2).
 // The PGD update and the APGD step themselves - every caller's, masked or not - are in vlm_attack_kernels.hip.
 // Arithmetic follows SURVEY.md Appendix A exactly: one IEEE fp32 rounding per reference op, no FMA contraction (this file is
 // built with -ffp-contract=off).  NaN / range asserts become bits of a device flag word that the host reads once after the loop.
@@ -181,6 +181,176 @@ square_accept_kernel(float* __restrict__ x_best, const float* __restrict__ x_new
         x_best[dst + e] = x_new[src + e];
 }
 
+// ---- Square Attack, L2 (autoattack/square.py:339-379) ---------------------------------------------------------------
+// One query in one launch, one workgroup of 1024 threads per still-robust image idx[a].  With delta = x_best - x (never stored):
+//   pass A, the image:    per channel sum delta^2 over window 1, over window 1 u window 2, and over the rest
+//   pass B, window 1:     raw = eta * sign[a, c] + delta / (1e-12 + |delta[win1]|_c), per channel sum raw^2
+//   pass C, window 1:     new = raw / (1e-12 + |raw|_c) * sqrt(max(eps^2 - |delta|^2, 0) / C + |delta[win1 u win2]|_c^2), sum new^2
+//   pass D, the image:    delta' = new on window 1, else 0 on window 2, else delta;  x_new = clamp(x + delta' / (|delta'| + 1e-12) * eps, 0, 1)
+// with |delta'|^2 = (pass A's rest) + (pass C's sums), a sum of non-negative terms.  Every sum is four lane partials -> wave
+// shuffles -> the 16 wave partials in LDS added in wave order: the same bits on every run, no atomics.  An image whose sums are
+// not finite (NaN / Inf in x, x_best, eta or sign: the reference's asserts, square.py:416-417) raises
+// RVLM_FLAG_SQUARE_NONFINITE and its row of x_new is x_best.  W % 4 == 0 and 16-byte pointers: 16-byte accesses; else scalar.
+constexpr int SQ_MAXC = 16;
+
+template <int N>
+__device__ __forceinline__ void sq_block_sum(float (&v)[N], float* red) {   // red: N * 16 floats; the totals land in every thread
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = wave_sum(v[k]);
+    __syncthreads();                                   // red may still be read from the previous reduction
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[k * 16 + (threadIdx.x >> 6)] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        float t = 0.0f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) t += red[k * 16 + i];
+        v[k] = t;
+    }
+}
+__device__ __forceinline__ bool sq_inside(int row, int col, int r0, int c0, int s) {
+    return row >= r0 && row < r0 + s && col >= c0 && col < c0 + s;
+}
+__device__ __forceinline__ bool sq_finite(float v) { return fabsf(v) <= 3.402823466e+38f; }
+
+__global__ void __launch_bounds__(1024)
+square_l2_propose_kernel(const float* __restrict__ x, const float* __restrict__ x_best, const long long* __restrict__ idx,
+                         int C, int H, int W, int vh, int vw, int vh2, int vw2, int s, float eps,
+                         const float* __restrict__ eta, const float* __restrict__ sign, float* __restrict__ x_new,
+                         int32_t* flags, int vec) {
+    __shared__ float red[3 * 16];
+    __shared__ float s_w1[SQ_MAXC], s_ws[SQ_MAXC], s_rest[SQ_MAXC], s_raw[SQ_MAXC], s_new[SQ_MAXC];
+    const int tid = threadIdx.x, HW = H * W, ss = s * s;
+    const long D = (long)C * HW;
+    const float* __restrict__ xs = x + (long)idx[blockIdx.x] * D;
+    const float* __restrict__ xb = x_best + (long)idx[blockIdx.x] * D;
+    float* __restrict__ xo = x_new + (long)blockIdx.x * D;
+    const float* __restrict__ sg = sign + (long)blockIdx.x * C;
+
+    // ---- pass A
+    for (int c = 0; c < C; ++c) {
+        const float* __restrict__ pa = xs + (long)c * HW;
+        const float* __restrict__ pb = xb + (long)c * HW;
+        float a1[4] = {0.0f, 0.0f, 0.0f, 0.0f}, au[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ar[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (vec) {
+            for (int u = tid; u < HW / 4; u += 1024) {
+                const f32x4 va = *reinterpret_cast<const f32x4*>(pa + 4 * u);
+                const f32x4 vb = *reinterpret_cast<const f32x4*>(pb + 4 * u);
+                const int row = (4 * u) / W, col = 4 * u - row * W;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = vb[k] - va[k], q = d * d;
+                    const bool in1 = sq_inside(row, col + k, vh, vw, s), in2 = sq_inside(row, col + k, vh2, vw2, s);
+                    a1[k] += in1 ? q : 0.0f;
+                    au[k] += (in1 || in2) ? q : 0.0f;
+                    ar[k] += (in1 || in2) ? 0.0f : q;
+                }
+            }
+        } else {
+            for (int e = tid; e < HW; e += 1024) {
+                const float d = pb[e] - pa[e], q = d * d;
+                const int row = e / W, col = e - row * W;
+                const bool in1 = sq_inside(row, col, vh, vw, s), in2 = sq_inside(row, col, vh2, vw2, s);
+                a1[0] += in1 ? q : 0.0f;
+                au[0] += (in1 || in2) ? q : 0.0f;
+                ar[0] += (in1 || in2) ? 0.0f : q;
+            }
+        }
+        float v[3] = {(a1[0] + a1[1]) + (a1[2] + a1[3]), (au[0] + au[1]) + (au[2] + au[3]), (ar[0] + ar[1]) + (ar[2] + ar[3])};
+        sq_block_sum<3>(v, red);
+        if (tid == 0) { s_w1[c] = v[0]; s_ws[c] = v[1]; s_rest[c] = v[2]; }
+    }
+    __syncthreads();
+    float img = 0.0f, rest = 0.0f;
+    for (int c = 0; c < C; ++c) { img += s_ws[c] + s_rest[c]; rest += s_rest[c]; }
+    const float nimg = sqrtf(img);
+    const float room = fmaxf(eps * eps - nimg * nimg, 0.0f) / (float)C;
+
+    // ---- pass B
+    for (int c = 0; c < C; ++c) {
+        const float* __restrict__ pa = xs + (long)c * HW;
+        const float* __restrict__ pb = xb + (long)c * HW;
+        const float den1 = 1e-12f + sqrtf(s_w1[c]), sgc = sg[c];
+        float v[1] = {0.0f};
+        for (int t = tid; t < ss; t += 1024) {
+            const int i = t / s, j = t - i * s, off = (vh + i) * W + vw + j;
+            const float raw = eta[t] * sgc + (pb[off] - pa[off]) / den1;
+            v[0] += raw * raw;
+        }
+        sq_block_sum<1>(v, red);
+        if (tid == 0) s_raw[c] = v[0];
+    }
+    __syncthreads();
+    // ---- pass C
+    for (int c = 0; c < C; ++c) {
+        const float* __restrict__ pa = xs + (long)c * HW;
+        const float* __restrict__ pb = xb + (long)c * HW;
+        const float den1 = 1e-12f + sqrtf(s_w1[c]), sgc = sg[c], den2 = 1e-12f + sqrtf(s_raw[c]);
+        const float nws = sqrtf(s_ws[c]), fac = sqrtf(room + nws * nws);
+        float v[1] = {0.0f};
+        for (int t = tid; t < ss; t += 1024) {
+            const int i = t / s, j = t - i * s, off = (vh + i) * W + vw + j;
+            const float raw = eta[t] * sgc + (pb[off] - pa[off]) / den1;
+            const float nw = raw / den2 * fac;
+            v[0] += nw * nw;
+        }
+        sq_block_sum<1>(v, red);
+        if (tid == 0) s_new[c] = v[0];
+    }
+    __syncthreads();
+    float total = rest;
+    bool bad = !sq_finite(img);
+    for (int c = 0; c < C; ++c) { total += s_new[c]; bad |= !sq_finite(s_raw[c]); }
+    bad |= !sq_finite(total);
+    if (bad) {                                                   // uniform over the workgroup
+        for (long e = tid; e < D; e += 1024) xo[e] = xb[e];
+        if (tid == 0 && flags) atomicOr(flags, RVLM_FLAG_SQUARE_NONFINITE);
+        return;
+    }
+    const float denf = sqrtf(total) + 1e-12f;
+
+    // ---- pass D
+    for (int c = 0; c < C; ++c) {
+        const float* __restrict__ pa = xs + (long)c * HW;
+        const float* __restrict__ pb = xb + (long)c * HW;
+        float* __restrict__ po = xo + (long)c * HW;
+        const float den1 = 1e-12f + sqrtf(s_w1[c]), sgc = sg[c], den2 = 1e-12f + sqrtf(s_raw[c]);
+        const float nws = sqrtf(s_ws[c]), fac = sqrtf(room + nws * nws);
+        if (vec) {
+            for (int u = tid; u < HW / 4; u += 1024) {
+                const f32x4 va = *reinterpret_cast<const f32x4*>(pa + 4 * u);
+                const f32x4 vb = *reinterpret_cast<const f32x4*>(pb + 4 * u);
+                const int row = (4 * u) / W, col = 4 * u - row * W;
+                f32x4 o;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float d = vb[k] - va[k];
+                    if (sq_inside(row, col + k, vh, vw, s))
+                        d = (eta[(row - vh) * s + (col + k - vw)] * sgc + d / den1) / den2 * fac;
+                    else if (sq_inside(row, col + k, vh2, vw2, s))
+                        d = 0.0f;
+                    o[k] = fminf(fmaxf(va[k] + d / denf * eps, 0.0f), 1.0f);
+                }
+                *reinterpret_cast<f32x4*>(po + 4 * u) = o;
+            }
+        } else {
+            for (int e = tid; e < HW; e += 1024) {
+                const int row = e / W, col = e - row * W;
+                const float xv = pa[e];
+                float d = pb[e] - xv;
+                if (sq_inside(row, col, vh, vw, s))
+                    d = (eta[(row - vh) * s + (col - vw)] * sgc + d / den1) / den2 * fac;
+                else if (sq_inside(row, col, vh2, vw2, s))
+                    d = 0.0f;
+                po[e] = fminf(fmaxf(xv + d / denf * eps, 0.0f), 1.0f);
+            }
+        }
+    }
+}
+
 extern "C" int rvlm_check_image_range(const float* x, size_t n, int32_t* flags,
                                       rvlm_stream_t stream) {
     RVLM_REQUIRE(x && flags, "rvlm_check_image_range: null pointer");
@@ -290,6 +460,21 @@ extern "C" int rvlm_square_linf_propose(const float* x, const float* x_best, con
     const int gx = (int)std::min<long>((n_img + 255) / 256, 64);
     hipLaunchKernelGGL(square_linf_propose_kernel, dim3(gx, n_active), dim3(256), 0, (hipStream_t)stream, x, x_best,
                        (const long long*)idx, C, H, W, vh, vw, s, eps, 2.0f * eps, sign, x_new);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+extern "C" int rvlm_square_l2_propose(const float* x, const float* x_best, const int64_t* idx, int n_active, int C, int H,
+                                      int W, int vh, int vw, int vh2, int vw2, int s, float eps, const float* eta,
+                                      const float* sign, float* x_new, int32_t* flags, rvlm_stream_t stream) {
+    RVLM_REQUIRE(x && x_best && idx && eta && sign && x_new && n_active > 0 && C > 0 && H > 0 && W > 0 &&
+                     (long)H * W <= 0x7fffffffL, "rvlm_square_l2_propose: bad args");
+    if (C > SQ_MAXC) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_square_l2_propose: more than 16 channels");
+    RVLM_REQUIRE(s >= 1 && vh >= 0 && vw >= 0 && vh + s <= H && vw + s <= W && vh2 >= 0 && vw2 >= 0 && vh2 + s <= H && vw2 + s <= W,
+                 "rvlm_square_l2_propose: window outside the image");
+    RVLM_REQUIRE(eps > 0.0f && eps <= 3.402823466e+38f, "rvlm_square_l2_propose: eps must be finite and positive");
+    const int vec = W % 4 == 0 && (((uintptr_t)x | (uintptr_t)x_best | (uintptr_t)x_new) & 15) == 0;
+    hipLaunchKernelGGL(square_l2_propose_kernel, dim3(n_active), dim3(1024), 0, (hipStream_t)stream, x, x_best,
+                       (const long long*)idx, C, H, W, vh, vw, vh2, vw2, s, eps, eta, sign, x_new, flags, vec);
     RVLM_CHECK_LAUNCH();
     return RVLM_OK;
 }

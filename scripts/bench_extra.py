@@ -3,7 +3,7 @@
 item 8, so that the headline harness only holds what BASELINE.json asks for):
 
   --norm l2               the L2 threat model of pgd / apgd_train / APGDAttack (eps = 3.0, PGD step eps/4)
-  --attack square         the black-box route (SquareAttack L-inf; forward passes only)
+  --attack square         the black-box route (SquareAttack, L-inf or with --norm l2 its L2 form; forward passes only)
   --model ViT-L-14-336 .. every other entry of robustvlm_amd.CONFIGS
 
 Same timed region, same JSON line (bench.main); `config.workload` says which of these it is and that it is not a BASELINE
@@ -33,8 +33,6 @@ class Extra:
                              "CLIP_eval/clip_robustbench.py); linf: eps = 4/255; l2: eps = 3.0, PGD step eps/4")
 
     def handles(self, args):
-        if args.norm != "linf" and args.attack == "square":
-            raise SystemExit("--attack square is L-inf only")
         return args.norm != "linf" or args.attack == "square"
 
     def make_step(self, args, R, eng, model, cfg, x, y, d0, e0, g, dev):
@@ -46,12 +44,17 @@ class Extra:
             clf = R.ClassificationModel(eng, T).eval()
             with torch.no_grad():
                 yc = clf(x).max(1)[1]
-            atk = R.SquareAttack(clf, norm="Linf", n_queries=it, eps=4 / 255, p_init=.8, n_restarts=1, seed=0, resc_schedule=False)
-            text = (f"black-box SquareAttack, {it} queries, eps=4/255 on {args.model} {args.precision} + 1000-class zero-shot head, "
+            l2 = args.norm == "l2"
+            eps = 3.0 if l2 else 4 / 255
+            atk = R.SquareAttack(clf, norm="L2" if l2 else "Linf", n_queries=it, eps=eps, p_init=.8, n_restarts=1, seed=0,
+                                 resc_schedule=False)
+            text = (f"black-box SquareAttack, {it} queries, eps={'3.0 (L2)' if l2 else '4/255'} on {args.model} {args.precision} + 1000-class zero-shot head, "
                     f"batch={B} per GPU (clip_robustbench.py --blackbox_only route; forward passes only, samples leave the batch "
                     f"once fooled); no BASELINE config")
             # at most it + 3 forwards (0.49 of a pair each; fewer once samples are fooled)
-            return (lambda: atk.perturb(x, yc)), text, "margin", 0.49 * (it + 3), lambda out: float((out - x).abs().max()) <= 4 / 255 + 1e-6
+            in_ball = (lambda out: float((out - x).flatten(1).norm(dim=1).max()) <= eps * (1 + 1e-5)) if l2 else \
+                (lambda out: float((out - x).abs().max()) <= 4 / 255 + 1e-6)
+            return (lambda: atk.perturb(x, yc)), text, "margin", 0.49 * (it + 3), in_ball
         eps, stepsize = 3.0, 0.75
         # the start point INSIDE the L2 ball (U(-4/255, 4/255) per pixel has |d0|_2 ~ 3.5 > eps, so the first
         # iteration - the one 'bf16+fp32-first' is built around - was evaluated outside the threat model)
