@@ -43,6 +43,8 @@ extern "C" {
 #define RVLM_HAS_VLM_ATTACKS 1
 /* RVLM_HAS_SQUARE_L2: rvlm_square_l2_propose (one query of the L2 Square Attack) and RVLM_FLAG_SQUARE_NONFINITE */
 #define RVLM_HAS_SQUARE_L2 1
+/* RVLM_HAS_SGD: rvlm_sgd_step (torch.optim.SGD with momentum, the trainer's --opt sgd) */
+#define RVLM_HAS_SGD 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -214,6 +216,16 @@ int rvlm_vit_backward_params_stages(rvlm_vit* h, const float* d_emb, int B, cons
 int rvlm_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
                     double lr, double beta1, double beta2, double eps, double weight_decay, int step,
                     float grad_scale, rvlm_stream_t stream);
+/* torch.optim.SGD single-tensor step (dampening 0, no Nesterov; --opt sgd, …clip.py:198-206) on flat fp32 buffers
+ * (RVLM_HAS_SGD).  Per element, in fp32, the double hyper-parameters rounded to fp32 first:
+ *     g = grads[i] * grad_scale;  d = g + weight_decay * p        (coupled weight decay, unlike AdamW's)
+ *     buf = first ? d : momentum * buf + d;  p = p - lr * buf     (momentum == 0: no buffer, p -= lr * d)
+ * `first` != 0 on the first step of a run (torch clones d into the buffer: it is written, not read).  momentum_buf may
+ * be NULL only when momentum == 0 and is then neither read nor written.  NULL params / grads, momentum < 0 and a NULL
+ * buffer with momentum > 0 are RVLM_ERR_ARG (nothing is launched); n == 0 is RVLM_OK without a launch.  Elements move in
+ * 16-byte accesses when all live pointers are 16-byte aligned, one float at a time otherwise, with identical results. */
+int rvlm_sgd_step(float* params, const float* grads, float* momentum_buf, size_t n, double lr, double momentum,
+                  double weight_decay, int first, float grad_scale, rvlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Losses (replace compute_loss / l2 / ce, …clip.py:495-528) - loss value and d loss / d emb.
@@ -652,7 +664,8 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * rvlm_vit_set_input_size, rvlm_resize_bicubic(_adjoint), rvlm_resize_taps (announced by RVLM_HAS_INPUT_RESIZE);
                            * rvlm_vit_forward_tokens, rvlm_vit_backward_input_tokens, rvlm_tokens_l2_loss_grad, rvlm_vit_tokens_fwd_inputgrad,
                            * rvlm_pgd_run_tokens, RVLM_FLAG_TOKENS_NONFINITE (announced by RVLM_HAS_TOKENS);
-                           * rvlm_square_l2_propose, RVLM_FLAG_SQUARE_NONFINITE (announced by RVLM_HAS_SQUARE_L2) */
+                           * rvlm_square_l2_propose, RVLM_FLAG_SQUARE_NONFINITE (announced by RVLM_HAS_SQUARE_L2);
+                           * rvlm_sgd_step (announced by RVLM_HAS_SGD) */
 
 #ifdef __cplusplus
 }

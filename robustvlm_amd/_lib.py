@@ -315,6 +315,11 @@ _SIGS.update({
     "rvlm_square_l2_propose": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_float, c_f32p, c_f32p, c_f32p, C.c_void_p, c_stream]),
 })
+_SIGS.update({
+    # torch.optim.SGD with momentum on flat fp32 buffers (csrc/train_kernels.hip; RVLM_HAS_SGD)
+    "rvlm_sgd_step": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float,
+                                c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

@@ -14,7 +14,8 @@ The optimizer file is ``torch.optim.AdamW(visual.parameters()).state_dict()`` as
 {index: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]}, …clip.py:240,471): the positional index follows
 open_clip's ``visual.parameters()`` order (robustvlm_amd.config.parameter_order), so a reference run resumes from a
 file written here and ``AdversarialTrainer.load_optimizer_state_dict`` reads the reference's files (and the name-keyed
-files round 1 of this package wrote).
+files round 1 of this package wrote).  A trainer built with ``opt="sgd"`` writes and reads ``torch.optim.SGD``'s file
+instead ({'state': {index: {'momentum_buffer'}}, ...}, …clip.py:198-206); the writer stores either as it is given.
 """
 from __future__ import annotations
 

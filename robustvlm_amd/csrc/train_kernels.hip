@@ -313,9 +313,76 @@ adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restri
     }
 }
 
+// torch.optim.SGD single-tensor update (dampening 0, no Nesterov, coupled weight decay), fp32 master weights:
+//   d = g + wd*p;  buf = first ? d : momentum*buf + d;  p -= lr*buf        (momentum == 0: no buffer, p -= lr*d)
+// Roundings as torch's ops place them: add(alpha=) is one fused multiply-add, mul_().add_() are two roundings.
+enum { SGD_NO_BUF = 0, SGD_FIRST = 1, SGD_MOMENTUM = 2 };
+template <int MODE>
+__device__ __forceinline__ void sgd_elem(float& p, float g, float& buf, float lr_neg, float momentum, float wd,
+                                         float grad_scale) {
+    float d = fmaf(wd, p, g * grad_scale);                           // grad.add(param, alpha=weight_decay)
+    if (MODE == SGD_MOMENTUM) d = momentum * buf + d;                // buf.mul_(momentum).add_(grad)
+    if (MODE != SGD_NO_BUF) buf = d;                                 // first step: buf = clone(grad)
+    p = fmaf(lr_neg, d, p);                                          // param.add_(buf, alpha=-lr)
+}
+// 20 B per element, a pure HBM stream: elements [0, 4*nvec) move as 16-byte accesses (the host passes nvec > 0 only when
+// every live pointer is 16-byte aligned), elements [4*nvec, n) one float at a time - the tail of an aligned call, or all
+// of a misaligned one.  Both loops run sgd_elem, so an element's result does not depend on the loop that took it.
+template <int MODE>
+__global__ void __launch_bounds__(256)
+sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, size_t n, size_t nvec,
+           float lr_neg, float momentum, float wd, float grad_scale) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
+    float4* __restrict__ p4 = reinterpret_cast<float4*>(p);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    float4* __restrict__ b4 = reinterpret_cast<float4*>(buf);
+    for (size_t i = tid; i < nvec; i += stride) {
+        float4 pv = p4[i], bv = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 gv = g4[i];
+        if (MODE == SGD_MOMENTUM) bv = b4[i];
+        sgd_elem<MODE>(pv.x, gv.x, bv.x, lr_neg, momentum, wd, grad_scale);
+        sgd_elem<MODE>(pv.y, gv.y, bv.y, lr_neg, momentum, wd, grad_scale);
+        sgd_elem<MODE>(pv.z, gv.z, bv.z, lr_neg, momentum, wd, grad_scale);
+        sgd_elem<MODE>(pv.w, gv.w, bv.w, lr_neg, momentum, wd, grad_scale);
+        p4[i] = pv;
+        if (MODE != SGD_NO_BUF) b4[i] = bv;
+    }
+    for (size_t i = nvec * 4 + tid; i < n; i += stride) {
+        float pi = p[i], bi = 0.f;
+        if (MODE == SGD_MOMENTUM) bi = buf[i];
+        sgd_elem<MODE>(pi, g[i], bi, lr_neg, momentum, wd, grad_scale);
+        p[i] = pi;
+        if (MODE != SGD_NO_BUF) buf[i] = bi;
+    }
+}
+
 }  // namespace rvlm
 
 using namespace rvlm;
+
+extern "C" int rvlm_sgd_step(float* params, const float* grads, float* momentum_buf, size_t n, double lr,
+                             double momentum, double weight_decay, int first, float grad_scale, rvlm_stream_t stream) {
+    RVLM_REQUIRE(params && grads && momentum >= 0.0 && (momentum_buf || momentum == 0.0),
+                 "rvlm_sgd_step: bad arguments (NULL params / grads, momentum < 0, or momentum > 0 without a buffer)");
+    if (n == 0) return RVLM_OK;
+    const int mode = momentum == 0.0 ? SGD_NO_BUF : (first ? SGD_FIRST : SGD_MOMENTUM);
+    float* buf = mode == SGD_NO_BUF ? nullptr : momentum_buf;        // momentum == 0: neither read nor written
+    const bool aligned = (((uintptr_t)params | (uintptr_t)grads | (uintptr_t)buf) & 15) == 0;
+    const size_t nvec = aligned ? n / 4 : 0;
+    size_t blocks = ((nvec ? nvec : n) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const float lr_neg = (float)(-lr), mom = (float)momentum, wd = (float)weight_decay;
+    const dim3 grid((int)blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == SGD_NO_BUF)
+        hipLaunchKernelGGL(sgd_kernel<SGD_NO_BUF>, grid, block, 0, s, params, grads, buf, n, nvec, lr_neg, mom, wd, grad_scale);
+    else if (mode == SGD_FIRST)
+        hipLaunchKernelGGL(sgd_kernel<SGD_FIRST>, grid, block, 0, s, params, grads, buf, n, nvec, lr_neg, mom, wd, grad_scale);
+    else
+        hipLaunchKernelGGL(sgd_kernel<SGD_MOMENTUM>, grid, block, 0, s, params, grads, buf, n, nvec, lr_neg, mom, wd, grad_scale);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
 
 extern "C" int rvlm_adamw_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, size_t n,
                                double lr, double beta1, double beta2, double eps, double weight_decay, int step,

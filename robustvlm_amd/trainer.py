@@ -13,12 +13,13 @@ Mirrors the step semantics of ``train_one_epoch`` (train/adversarial_training_cl
     cos-sim-clean / cos-sim / acc / racc                (logging, no grad)      :368-387
     every eval_freq steps: acc / racc / cos-sim under a 50-step supervised APGD :389-424
 
-with AdamW (lr 1e-5, wd 1e-4, :196-197) and open_clip's cosine_lr with linear warm-up (:211).
+with AdamW (lr 1e-5, wd 1e-4, :196-197) or, with ``opt="sgd"``, SGD with momentum (``--opt sgd`` / ``--momentum_sgd``,
+:198-206), and open_clip's cosine_lr with linear warm-up (:211).
 The reference wraps the model in single-process nn.DataParallel (:184-191), whose replica gradients are reduced
 inside ``backward``; here every rank owns one GPU and its shard of the batch, the attack needs no communication, and
 the gradient all-reduce (RCCL through torch.distributed) runs in ``n_buckets`` contiguous slices of ONE flat fp32
 buffer, each launched as soon as the backward stages that fill it are done, so that it overlaps the remaining stages
-(rvlm_vit_backward_params_stages); the 1/world_size scaling is fused into the AdamW kernel.
+(rvlm_vit_backward_params_stages); the 1/world_size scaling is fused into the optimizer kernel.
 """
 from __future__ import annotations
 
@@ -106,14 +107,23 @@ class AdversarialTrainer:
                  iterations_adv=10, stepsize_adv=1 / 255, output_normalize=False, clean_weight=0.0,
                  embedding_text_labels_norm=None, betas=(0.9, 0.999), adam_eps=1e-8, device=None,
                  loss_clean="l2", trades=False, n_buckets=4, metrics=True, process_group=None,
-                 always_reduce=False):
+                 always_reduce=False, opt="adamw", momentum_sgd=0.9):
+        if opt not in ("adamw", "sgd"):                           # …clip.py:196-206; before any device work
+            raise ValueError(f"Optimizer {opt} not supported.")
+        self.opt, self.momentum_sgd = opt, float(momentum_sgd)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.cfg = cfg
         self.lib = L.load()
         self.params = FlatParams(cfg, state_dict, self.device)
         self.grads = self.params.like()
-        self.exp_avg = torch.zeros_like(self.params.flat)
-        self.exp_avg_sq = torch.zeros_like(self.params.flat)
+        if opt == "adamw":
+            self.exp_avg = torch.zeros_like(self.params.flat)
+            self.exp_avg_sq = torch.zeros_like(self.params.flat)
+        else:
+            # torch.optim.SGD keeps one buffer per parameter, and none at all without momentum
+            self.momentum_buffer = torch.zeros_like(self.params.flat) if self.momentum_sgd != 0 else None
+            # torch clones the first step's gradient into the buffer: true until a step has run or buffers were loaded
+            self._sgd_first = True
         self.engine = VitEngine(cfg, self.params.views, precision=precision, max_batch=batch_size,
                                 device=self.device, trainable=True)
         self.engine_orig = VitEngine(cfg, self.params.views, precision=precision, max_batch=batch_size,
@@ -193,7 +203,7 @@ class AdversarialTrainer:
 
     def _shard_weight(self, n_local: int, global_batch: int | None = None) -> float:
         """The reference's loss is the mean over the GLOBAL batch (DataParallel gathers the outputs first, …clip.py:
-        184-191).  Here every rank takes the mean over its shard and AdamW divides the summed gradients by world_size;
+        184-191).  Here every rank takes the mean over its shard and the optimizer divides the summed gradients by world_size;
         the factor n_local * world / n_global makes that exact for uneven shards too (1.0 for equal ones).  A caller
         that knows the global batch size passes it: no collective and no host sync in front of the backward then."""
         if self.world == 1:
@@ -217,6 +227,23 @@ class AdversarialTrainer:
             n = n.to(self.device)
         dist.all_reduce(n, op=dist.ReduceOp.SUM, group=self.pg)
         return n_local * self.world / float(n.item())
+
+    def _optimizer_step(self):
+        """optimizer.step() (…clip.py:362) over the flat buffers at ``cur_lr``; the 1 / world of the summed gradients
+        goes in as grad_scale."""
+        with torch.cuda.device(self.device):
+            if self.opt == "sgd":
+                L.check(self.lib.rvlm_sgd_step(self.params.flat.data_ptr(), self.grads.flat.data_ptr(),
+                                               L.ptr(self.momentum_buffer), self.params.numel, float(self.cur_lr),
+                                               self.momentum_sgd, self.wd, int(self._sgd_first), 1.0 / self.world,
+                                               L.stream_ptr()), "rvlm_sgd_step")
+                self._sgd_first = False
+                return
+            b1, b2 = self.betas
+            L.check(self.lib.rvlm_adamw_step(self.params.flat.data_ptr(), self.grads.flat.data_ptr(),
+                                             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.params.numel,
+                                             float(self.cur_lr), b1, b2, self.adam_eps, self.wd, self.step_total,
+                                             1.0 / self.world, L.stream_ptr()), "rvlm_adamw_step")
 
     @torch.no_grad()
     def _cos_mean(self, a, b):
@@ -293,12 +320,7 @@ class AdversarialTrainer:
         loss, emb_adv = self._loss_backward(data_adv, targets, e_ref, self.loss, self.T, (1.0 - cw) * wshard,
                                             accumulate, dp)                      # …clip.py:349-361
         self.step_total += 1
-        b1, b2 = self.betas
-        with torch.cuda.device(self.device):
-            L.check(self.lib.rvlm_adamw_step(self.params.flat.data_ptr(), self.grads.flat.data_ptr(),
-                                             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.params.numel,
-                                             float(self.cur_lr), b1, b2, self.adam_eps, self.wd, self.step_total,
-                                             1.0 / self.world, L.stream_ptr()), "rvlm_adamw_step")
+        self._optimizer_step()
         self.engine.load_state_dict(self.params.views)       # refresh the bf16 / transposed GEMM copies
         lr_used = self.cur_lr
         self.cur_lr = cosine_lr_value(self.step_total, self.lr, self.warmup, self.steps)   # scheduler(step_total)
@@ -388,16 +410,25 @@ class AdversarialTrainer:
         self._verify_pending_global_batch()
         return self.params.state_dict()
 
-    # -- optimizer state: the file torch.optim.AdamW.state_dict() would write for visual.parameters() ---------------
+    # -- optimizer state: the file torch.optim.AdamW / SGD .state_dict() would write for visual.parameters() ---------
     def optimizer_state_dict(self):
-        """``torch.optim.AdamW(visual.parameters()).state_dict()`` layout (…clip.py:196-197,240,471): 'state' keyed by the
-        positional index of ``visual.parameters()``, one param group - a reference run can resume from it and vice
-        versa.  'param_names' (index -> key) is added for readers without the module (torch ignores it)."""
+        """``torch.optim.AdamW(visual.parameters()).state_dict()`` layout (…clip.py:196-197,240,471), or
+        ``torch.optim.SGD``'s for ``opt="sgd"``: 'state' keyed by the positional index of ``visual.parameters()``, one
+        param group - a reference run can resume from it and vice versa.  'param_names' (index -> key) is added for
+        readers without the module (torch ignores it)."""
         order = parameter_order(self.cfg)
 
         def piece(flat, k):
             o, c = self.params.offsets[k]
             return flat[o:o + c].view(self.params.shapes[k]).clone()
+        if self.opt == "sgd":
+            # torch creates a parameter's entry in its first step, and none without momentum
+            has_buf = self.momentum_buffer is not None and not self._sgd_first
+            state = {i: {"momentum_buffer": piece(self.momentum_buffer, k)} for i, k in enumerate(order)} if has_buf else {}
+            group = {"lr": self.cur_lr, "momentum": self.momentum_sgd, "dampening": 0, "weight_decay": self.wd,
+                     "nesterov": False, "maximize": False, "foreach": None, "differentiable": False, "fused": None,
+                     "params": list(range(len(order)))}
+            return {"state": state, "param_groups": [group], "param_names": order}
         state = {i: {"step": torch.tensor(float(self.step_total)), "exp_avg": piece(self.exp_avg, k),
                      "exp_avg_sq": piece(self.exp_avg_sq, k)} for i, k in enumerate(order)}
         group = {"lr": self.cur_lr, "betas": tuple(self.betas), "eps": self.adam_eps, "weight_decay": self.wd,
@@ -408,34 +439,63 @@ class AdversarialTrainer:
     def load_optimizer_state_dict(self, sd, start_step=None):
         """Resume (…clip.py:207-208,219): restores the moments and the step counter; the LR schedule is a pure
         function of the step.  Accepts torch's AdamW layout (from this trainer or from a reference run) and the
-        name-keyed layout round 1 of this package wrote."""
-        if "state" in sd and "param_groups" in sd:
-            order = parameter_order(self.cfg)
-            if len(sd["state"]) not in (0, len(order)):
-                raise ValueError(f"optimizer state has {len(sd['state'])} entries, the tower {len(order)} parameters")
+        name-keyed layout round 1 of this package wrote; an SGD trainer accepts torch's SGD layout, whose file holds no
+        step counter: ``start_step`` (the reference's --start_step next to --optimizer_state) is then required."""
+        torch_layout = "state" in sd and "param_groups" in sd
+        group = sd["param_groups"][0] if torch_layout and sd["param_groups"] else {}
+        file_opt = "adamw" if (not torch_layout or "betas" in group) else "sgd" if "momentum" in group else None
+        if file_opt is not None and file_opt != self.opt:
+            raise ValueError(f"optimizer state is a file of {file_opt}, this trainer's optimizer is {self.opt}: resume it with "
+                             f"opt='{file_opt}'")
+        if self.opt == "sgd":
+            if sd["state"] and start_step is None:
+                raise ValueError("torch.optim.SGD's file holds no step counter: pass start_step (--start_step) with it")
+            if sd["state"] and self.momentum_buffer is None:
+                raise ValueError("optimizer state holds momentum buffers, this trainer was built with momentum_sgd=0")
+            for k, st in self._torch_state_entries(sd, "momentum_buffer"):
+                self._copy_piece(self.momentum_buffer, k, st["momentum_buffer"])
+            self._sgd_first = not sd["state"]        # a file without buffers is an optimizer that has not stepped
             step = 0
-            for i, k in enumerate(order):
-                if i not in sd["state"]:
-                    continue
-                st, (o, c) = sd["state"][i], self.params.offsets[k]
-                if tuple(st["exp_avg"].shape) != tuple(self.params.shapes[k]):
-                    raise ValueError(f"optimizer state {i} has shape {tuple(st['exp_avg'].shape)}, parameter {k} "
-                                     f"{tuple(self.params.shapes[k])}: not visual.parameters() order")
-                self.exp_avg[o:o + c].copy_(st["exp_avg"].reshape(-1).to(self.device))
-                self.exp_avg_sq[o:o + c].copy_(st["exp_avg_sq"].reshape(-1).to(self.device))
+        elif torch_layout:
+            step = 0
+            for k, st in self._torch_state_entries(sd, "exp_avg"):
+                self._copy_piece(self.exp_avg, k, st["exp_avg"])
+                self._copy_piece(self.exp_avg_sq, k, st["exp_avg_sq"])
                 step = int(float(st["step"]))
-            file_lr = sd["param_groups"][0].get("lr") if sd["param_groups"] else None
         else:
-            for k, (o, c) in self.params.offsets.items():
-                self.exp_avg[o:o + c].copy_(sd["exp_avg"][k].reshape(-1).to(self.device))
-                self.exp_avg_sq[o:o + c].copy_(sd["exp_avg_sq"][k].reshape(-1).to(self.device))
+            for k in self.params.offsets:
+                self._copy_piece(self.exp_avg, k, sd["exp_avg"][k])
+                self._copy_piece(self.exp_avg_sq, k, sd["exp_avg_sq"][k])
             step = int(sd["step"])
-            file_lr = None
         self.step_total = int(step if start_step is None else start_step)
         # optimizer.load_state_dict restores the param group's lr (…clip.py:207-208) = what the scheduler left behind
         # when the file was written; the next scheduler call comes after the first resumed step
+        file_lr = group.get("lr")
         self.cur_lr = float(file_lr) if file_lr is not None else cosine_lr_value(self.step_total, self.lr, self.warmup,
                                                                                  self.steps)
+
+    def _torch_state_entries(self, sd, field):
+        """(key, entry) of a torch-layout optimizer file in ``visual.parameters()`` order; the entry count, the presence of
+        ``field`` (what tells the two optimizers' files apart) and its shape are checked."""
+        order = parameter_order(self.cfg)
+        if len(sd["state"]) not in (0, len(order)):
+            raise ValueError(f"optimizer state has {len(sd['state'])} entries, the tower {len(order)} parameters")
+        other = "sgd" if self.opt == "adamw" else "adamw"
+        for i, k in enumerate(order):
+            if i not in sd["state"]:
+                continue
+            st = sd["state"][i]
+            if field not in st:
+                raise ValueError(f"optimizer state {i} holds {sorted(st)}, no {field}: not a file of {self.opt} (this "
+                                 f"trainer's optimizer); a file of {other} needs a trainer with opt='{other}'")
+            if tuple(st[field].shape) != tuple(self.params.shapes[k]):
+                raise ValueError(f"optimizer state {i} has shape {tuple(st[field].shape)}, parameter {k} "
+                                 f"{tuple(self.params.shapes[k])}: not visual.parameters() order")
+            yield k, st
+
+    def _copy_piece(self, flat, k, t):
+        o, c = self.params.offsets[k]
+        flat[o:o + c].copy_(t.reshape(-1).to(self.device))
 
     def load_state_dict(self, state_dict):
         """Resume the model weights (…clip.py:98-103): both engines' GEMM copies are refreshed; ``model_orig`` keeps the
