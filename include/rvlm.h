@@ -45,6 +45,9 @@ extern "C" {
 #define RVLM_HAS_SQUARE_L2 1
 /* RVLM_HAS_SGD: rvlm_sgd_step (torch.optim.SGD with momentum, the trainer's --opt sgd) */
 #define RVLM_HAS_SGD 1
+/* RVLM_HAS_TOKEN_TRAINING: weight gradients through the token door - rvlm_vit_forward_tokens(save = 2),
+ * rvlm_vit_backward_params_tokens(_stages), rvlm_tokens_cosine */
+#define RVLM_HAS_TOKEN_TRAINING 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -452,7 +455,9 @@ enum { RVLM_TOKENS_ALL = 0, RVLM_TOKENS_PATCH = 1 };   /* rows of the token loss
 /* out_tokens [B, S, W] fp32.  ln_post = 1: ln_post applied to every row first (releases of open_clip that normalise the tokens
  * they return); 0: the raw residual stream.  out_emb (optional, depth == layers only): the pooled embedding [B, D], un-normalised,
  * the bits rvlm_vit_forward gives on an fp32-storage handle.  save = 1 keeps the activations for rvlm_vit_backward_input_tokens
- * (the first ln_post pass of a handle allocates the row statistics it needs: 2 floats per token row). */
+ * (the first ln_post pass of a handle allocates the row statistics it needs: 2 floats per token row).  save = 2
+ * (RVLM_HAS_TOKEN_TRAINING; `trainable` handles, RVLM_ERR_ARG on any other) additionally keeps the inputs of every linear layer of
+ * blocks 0 .. depth - 1 for rvlm_vit_backward_params_tokens; rvlm_vit_backward_input_tokens reads such a pass too. */
 int rvlm_vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, int B, int depth, int ln_post, int save,
                             float* out_tokens, float* out_emb, rvlm_stream_t stream);
 
@@ -462,6 +467,30 @@ int rvlm_vit_forward_tokens(rvlm_vit* h, const float* x, const float* delta, int
  * (rvlm_vit_backward_input, _params, _input_from) return RVLM_ERR_STATE after a token forward. */
 int rvlm_vit_backward_input_tokens(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B, float* grad_x,
                                    rvlm_stream_t stream);
+
+/* Weight gradients through the token door (RVLM_HAS_TOKEN_TRAINING): for the token pass saved last with save = 2 on a `trainable`
+ * handle, writes (accumulate == 0) or adds (accumulate != 0) d(<d_tokens, tokens> + <d_emb, emb>) / d(param) into the fp32 tensors
+ * `grads` points to.  d_tokens [B, S, W] fp32, required; d_emb [B, D] optional, depth == layers only (else RVLM_ERR_ARG).  The saved
+ * pass's ln_post flag is honoured.  No input gradient is produced.  Parameters the cotangent cannot reach - proj unless d_emb is
+ * given, ln_post.* unless the pass applied ln_post or d_emb is given, every block >= depth - are zero-filled when accumulate == 0
+ * and left untouched otherwise.  RVLM_ERR_STATE: handle not trainable; the last saved forward is pooled, a token pass with
+ * save != 2, or of another B.  The pooled backwards keep returning RVLM_ERR_STATE after any token forward. */
+int rvlm_vit_backward_params_tokens(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B, const rvlm_vit_weights* grads,
+                                    int accumulate, rvlm_stream_t stream);
+/* The same pass in the stages of rvlm_vit_backward_params_stages (same numbers, same in-order rule; stage 0 restarts).  Stage 0
+ * seeds the residual-gradient stream from d_tokens (through ln_post's backward over every row where the pass applied it, plus the
+ * pooled path's class rows when d_emb is given) and owns proj / ln_post; an unreached parameter is zero-filled by the stage that
+ * owns it. */
+int rvlm_vit_backward_params_tokens_stages(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B,
+                                           const rvlm_vit_weights* grads, int accumulate, int stage_begin, int stage_end,
+                                           rvlm_stream_t stream);
+
+/* Logging metric of the token training step, the token twin of rvlm_cosine_rows (RVLM_HAS_TOKEN_TRAINING): out_per_image[b] = the
+ * mean over the selected rows of F.cosine_similarity(tokens[b, s], ref_tokens[b, s - select]) (eps 1e-8: a.b / sqrt(max(|a|^2 |b|^2,
+ * 1e-16))); shapes and `select` as in rvlm_tokens_l2_loss_grad.  out_mean (optional) = their mean over b.  scratch: B * ceil(S / 8)
+ * floats.  Fixed summation order (bit-reproducible), no atomics.  W % 8 == 0, 16-byte aligned pointers. */
+int rvlm_tokens_cosine(const float* tokens, const float* ref_tokens, int B, int S, int W, int select, float* out_per_image,
+                       float* out_mean, float* scratch, rvlm_stream_t stream);
 
 /* FARE's embedding loss (train/adversarial_training_clip.py:509-521) over the tokens the VLM reads, fused with the start of the
  * backward: loss_per_sample[b] = sum over the selected rows and W of (tokens - ref_tokens)^2, ref_tokens [B, S - select, W];
@@ -665,7 +694,9 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * rvlm_vit_forward_tokens, rvlm_vit_backward_input_tokens, rvlm_tokens_l2_loss_grad, rvlm_vit_tokens_fwd_inputgrad,
                            * rvlm_pgd_run_tokens, RVLM_FLAG_TOKENS_NONFINITE (announced by RVLM_HAS_TOKENS);
                            * rvlm_square_l2_propose, RVLM_FLAG_SQUARE_NONFINITE (announced by RVLM_HAS_SQUARE_L2);
-                           * rvlm_sgd_step (announced by RVLM_HAS_SGD) */
+                           * rvlm_sgd_step (announced by RVLM_HAS_SGD);
+                           * rvlm_vit_forward_tokens(save = 2), rvlm_vit_backward_params_tokens(_stages), rvlm_tokens_cosine
+                           * (announced by RVLM_HAS_TOKEN_TRAINING) */
 
 #ifdef __cplusplus
 }

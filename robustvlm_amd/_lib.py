@@ -320,6 +320,13 @@ _SIGS.update({
     "rvlm_sgd_step": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_size_t, C.c_double, C.c_double, C.c_double, C.c_int, C.c_float,
                                 c_stream]),
 })
+_SIGS.update({
+    # weight gradients through the token door (csrc/engine_backward.hip, csrc/token_kernels.hip; RVLM_HAS_TOKEN_TRAINING)
+    "rvlm_vit_backward_params_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.POINTER(VitWeightsC), C.c_int, c_stream]),
+    "rvlm_vit_backward_params_tokens_stages": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.POINTER(VitWeightsC), C.c_int,
+                                                         C.c_int, C.c_int, c_stream]),
+    "rvlm_tokens_cosine": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

@@ -241,11 +241,30 @@ static int embed_bwd_params(rvlm_vit* h, const SavedView& v, const ParamSink& k,
     return wgrad<T>(h, s, h->d_patch, W, h->A0, h->Kpad, M0, W, h->Kp, grad_of(k.gw->conv1_weight), h->Kp, acc);
 }
 
+// Gradients of parameters a token cotangent cannot reach: zeros where the pass writes, untouched where it adds
+static int zero_unreached(const ParamSink& k, float* g, size_t n, hipStream_t s) {
+    if (!k.accumulate) RVLM_HIP(hipMemsetAsync(g, 0, n * 4, s));
+    return RVLM_OK;
+}
+static int zero_block_grads(rvlm_vit* h, const ParamSink& k, int l, hipStream_t s) {
+    const size_t W = (size_t)h->W;
+    const rvlm_vit_block_weights& g = k.gw->blocks_host[l];
+    const struct { const float* p; size_t n; } t[] = {
+        {g.ln_1_weight, W}, {g.ln_1_bias, W}, {g.attn_in_proj_weight, 3 * W * W}, {g.attn_in_proj_bias, 3 * W},
+        {g.attn_out_proj_weight, W * W}, {g.attn_out_proj_bias, W}, {g.ln_2_weight, W}, {g.ln_2_bias, W},
+        {g.mlp_c_fc_weight, 4 * W * W}, {g.mlp_c_fc_bias, 4 * W}, {g.mlp_c_proj_weight, 4 * W * W}, {g.mlp_c_proj_bias, W}};
+    for (const auto& e : t) { int rc = zero_unreached(k, grad_of(e.p), e.n, s); if (rc) return rc; }
+    return RVLM_OK;
+}
+
 // The backward walker: head (or token seed), blocks from the top down, embeddings - on h's kernels, scratch and weights, of the saved
 // forward `v`.  Without a sink: the input gradient into grad_x.  With a sink: the parameter pass - the same chain with each linear's
 // weight gradient issued before its dgrad and each LayerNorm's before its backward, from the inputs a save-mode-2 forward kept on h
 // (ln1_out, ln2_out, g_act_l, tokens), cut into the sink's stages, always on the fp32 residual-gradient stream, and WITHOUT profile
 // scopes (a training step's classes are not part of rvlm_vit_get_profile).
+// With a token seed AND a sink: the parameter pass of a token forward (Saved::TokensParams).  Stage 0 seeds the stream from d_tokens
+// and owns proj / ln_post; the stages of blocks >= depth own parameters the cotangent cannot reach.  Unreached parameters are
+// zero-filled by their stage when the pass writes (accumulate == 0) and left alone when it adds.
 // fp32_dres: keep the fp32 stream where the handle would run the bf16-only one (rvlm_vit::lp_dres).
 template <typename T>
 static int backward_impl(rvlm_vit* h, const SavedView& v, const float* d_emb, int B, float* grad_x, hipStream_t s, bool fp32_dres = false,
@@ -263,10 +282,21 @@ static int backward_impl(rvlm_vit* h, const SavedView& v, const float* d_emb, in
     T* const dres_lp = LP ? (T*)h->dres_lp : nullptr;
     int rc;
     h->lin.a3_of = nullptr;
-    if (ts) {
+    if (ts && st0 <= 0 && st1 > 0) {
         // token pass: the stream starts as the token cotangent (every row live), plus the pooled path's class rows when d_emb is given
-        PROF("tokens_seed", d_emb ? 2.0 * B * W * D : 0.0, (double)M * W * (4 + (dres32 ? 4 : 0) + (LP ? sizeof(T) : 0)));
-        if (d_emb && (rc = head_dpooled(h, v, d_emb, B, nullptr, s))) return rc;      // (a token pass's embedding is un-normalised)
+        PROF_IF(prof, "tokens_seed", d_emb ? 2.0 * B * W * D : 0.0, (double)M * W * (4 + (dres32 ? 4 : 0) + (LP ? sizeof(T) : 0)));
+        if (d_emb && (rc = head_dpooled(h, v, d_emb, B, sink, s))) return rc;      // (a token pass's embedding is un-normalised)
+        if (sink) {      // stage 0's parameters: proj and ln_post from the pooled path (above), ln_post over every row from the tokens
+            if (!d_emb && (rc = zero_unreached(*sink, grad_of(sink->gw->proj), (size_t)W * D, s))) return rc;
+            if (ts->ln_post) {
+                if ((rc = ln_param_grad<float>(ts->d_tokens, W, v.xs[2 * Ltop], W, h->tok_mean, h->tok_rstd, M, W,
+                                               grad_of(sink->gw->ln_post_weight), grad_of(sink->gw->ln_post_bias), (d_emb || acc) ? 1 : 0,
+                                               h->red_scratch, h->red_floats, s))) return rc;
+            } else if (!d_emb) {
+                if ((rc = zero_unreached(*sink, grad_of(sink->gw->ln_post_weight), (size_t)W, s))) return rc;
+                if ((rc = zero_unreached(*sink, grad_of(sink->gw->ln_post_bias), (size_t)W, s))) return rc;
+            }
+        }
         if (ts->d_tokens && !ts->ln_post) {
             const float* cls_add = nullptr;
             if (d_emb) {  // ln_post'(d_pooled) into the class rows of the fp32 buffer (a scratch where the stream is bf16 only): the seed
@@ -284,7 +314,7 @@ static int backward_impl(rvlm_vit* h, const SavedView& v, const float* d_emb, in
                                               dres_lp, W, 0, M, W, s))) return rc;
             if (d_emb && (rc = head_lnpost_bwd<T>(h, v, dres32, dres_lp, 1, B, s))) return rc;
         }
-    } else if (st0 <= 0 && st1 > 0) {
+    } else if (!ts && st0 <= 0 && st1 > 0) {
         PROF_IF(prof, "head_bwd", 2.0 * B * W * D, 0);
         if ((rc = head_dpooled(h, v, d_emb, B, sink, s))) return rc;
         if (!tail) {   // with the class-token tail the last block's ln_1 backward overwrites the other rows
@@ -294,6 +324,8 @@ static int backward_impl(rvlm_vit* h, const SavedView& v, const float* d_emb, in
         if ((rc = head_lnpost_bwd<T>(h, v, dres32, dres_lp, 0, B, s))) return rc;
     }
     const void* dres_A = LP ? (const void*)h->dres_lp : (const void*)h->dres;
+    for (int l = L - 1; sink && l >= Ltop; --l)      // blocks the token pass did not run
+        if (L - l >= st0 && L - l < st1 && (rc = zero_block_grads(h, *sink, l, s))) return rc;
     for (int l = Ltop - 1; l >= 0; --l) {
         if (L - l < st0 || L - l >= st1) continue;
         Layer& y = h->layers[l];
@@ -377,20 +409,24 @@ int saved_check(const rvlm_vit* h, Reader r, int B, const char* who) {
     case Reader::Input:
         if (!have) return fail(RVLM_ERR_STATE, "rvlm_vit_backward_input: no saved forward for this batch size");
         if (m == Saved::ForPeer) return fail(RVLM_ERR_STATE, "backward: the saved forward was run for another handle's backward (no probabilities kept)");
-        if (m == Saved::Tokens) return fail(RVLM_ERR_STATE, "backward: the saved forward is a token pass (rvlm_vit_backward_input_tokens differentiates it)");
+        if (is_token_pass(m)) return fail(RVLM_ERR_STATE, "backward: the saved forward is a token pass (rvlm_vit_backward_input_tokens differentiates it)");
         break;
     case Reader::Params:
         if (!have || m != Saved::Params) return fail(RVLM_ERR_STATE, std::string(who) + ": needs a forward with save_for_backward == 2 for this batch");
         break;
     case Reader::Tokens:
-        if (!have || m != Saved::Tokens)
-            return fail(RVLM_ERR_STATE, h->saved_B > 0 && m != Saved::Tokens
+        if (!have || !is_token_pass(m))
+            return fail(RVLM_ERR_STATE, h->saved_B > 0 && !is_token_pass(m)
                             ? "rvlm_vit_backward_input_tokens: the saved forward is a pooled pass (rvlm_vit_backward_input differentiates it)"
                             : "rvlm_vit_backward_input_tokens: no saved token forward for this batch size");
         break;
+    case Reader::TokensParams:
+        if (!have || m != Saved::TokensParams)
+            return fail(RVLM_ERR_STATE, std::string(who) + ": needs a token forward with save == 2 for this batch");
+        break;
     case Reader::Handoff:
         if (!have) return fail(RVLM_ERR_STATE, "handoff: no saved forward for this batch size on the fp32-storage handle");
-        if (m == Saved::Tokens) return fail(RVLM_ERR_STATE, "handoff: the saved forward is a token pass (the handoff precisions take pooled passes only)");
+        if (is_token_pass(m)) return fail(RVLM_ERR_STATE, "handoff: the saved forward is a token pass (the handoff precisions take pooled passes only)");
         break;
     }
     return RVLM_OK;
@@ -407,6 +443,10 @@ int vit_backward(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStrea
 int vit_backward_params(rvlm_vit* h, const float* d_emb, int B, const ParamSink& sink, hipStream_t s) {
     return h->lin.bf16 ? backward_impl<bf16_t>(h, own_view(h), d_emb, B, nullptr, s, true, nullptr, &sink)
                    : backward_impl<float>(h, own_view(h), d_emb, B, nullptr, s, true, nullptr, &sink);
+}
+int vit_backward_params_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int B, const ParamSink& sink, hipStream_t s) {
+    return h->lin.bf16 ? backward_impl<bf16_t>(h, own_view(h), d_emb, B, nullptr, s, true, &ts, &sink)
+                   : backward_impl<float>(h, own_view(h), d_emb, B, nullptr, s, true, &ts, &sink);
 }
 
 // HANDOFF (round 6): the input gradient of the forward SAVED ON `hx` (an fp32-storage handle: x3 or fp32 precision) evaluated by the
@@ -496,4 +536,38 @@ extern "C" int rvlm_vit_backward_input_tokens(rvlm_vit* h, const float* d_tokens
     int rc = saved_check(h, Reader::Tokens, B); if (rc) return rc;
     RVLM_REQUIRE(!d_emb || h->saved_depth == h->L, "rvlm_vit_backward_input_tokens: d_emb needs a token pass of depth == layers");
     return vit_backward_tokens(h, TokSeed{d_tokens, h->saved_depth, h->saved_lnpost}, d_emb, B, grad_x, (hipStream_t)stream);
+}
+
+// ---- token parameter pass (RVLM_HAS_TOKEN_TRAINING) ---------------------------------------------------------------------------
+static int params_tokens_check(rvlm_vit* h, const float* d_emb, int B, const char* who) {
+    if (!h->trainable) return fail(RVLM_ERR_STATE, std::string(who) + ": handle was not created trainable");
+    int rc = saved_check(h, Reader::TokensParams, B, who); if (rc) return rc;
+    if (d_emb && h->saved_depth != h->L) return fail(RVLM_ERR_ARG, std::string(who) + ": d_emb needs a token pass of depth == layers");
+    return RVLM_OK;
+}
+
+extern "C" int rvlm_vit_backward_params_tokens(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B,
+                                               const rvlm_vit_weights* grads, int accumulate, rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && d_tokens && grads && grads->blocks_host, "rvlm_vit_backward_params_tokens: null argument");
+    int rc = params_tokens_check(h, d_emb, B, "rvlm_vit_backward_params_tokens"); if (rc) return rc;
+    h->next_param_stage = h->L + 2;
+    return vit_backward_params_tokens(h, TokSeed{d_tokens, h->saved_depth, h->saved_lnpost}, d_emb, B,
+                                      ParamSink{grads, accumulate, 0, h->L + 2}, (hipStream_t)stream);
+}
+
+extern "C" int rvlm_vit_backward_params_tokens_stages(rvlm_vit* h, const float* d_tokens, const float* d_emb, int B,
+                                                      const rvlm_vit_weights* grads, int accumulate, int stage_begin, int stage_end,
+                                                      rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && d_tokens && grads && grads->blocks_host, "rvlm_vit_backward_params_tokens_stages: null argument");
+    int rc = params_tokens_check(h, d_emb, B, "rvlm_vit_backward_params_tokens_stages"); if (rc) return rc;
+    RVLM_REQUIRE(stage_begin >= 0 && stage_begin < stage_end && stage_end <= h->L + 2,
+                 "rvlm_vit_backward_params_tokens_stages: need 0 <= stage_begin < stage_end <= layers + 2");
+    // (the in-order rule of rvlm_vit_backward_params_stages: the stages hand the residual gradient to each other through the handle)
+    if (stage_begin != 0 && stage_begin != h->next_param_stage)
+        return fail(RVLM_ERR_STATE, "rvlm_vit_backward_params_tokens_stages: stages of one backward must run in order from 0 "
+                                    "(stage_begin does not continue the previous call's stage_end)");
+    rc = vit_backward_params_tokens(h, TokSeed{d_tokens, h->saved_depth, h->saved_lnpost}, d_emb, B,
+                                    ParamSink{grads, accumulate, stage_begin, stage_end}, (hipStream_t)stream);
+    h->next_param_stage = rc == RVLM_OK ? stage_end : -1;
+    return rc;
 }

@@ -218,7 +218,7 @@ static int forward_impl(rvlm_vit* h, const float* x, const float* delta, int B, 
         }
     }
     if (save) { h->saved_B = B; h->saved_norm = normalize != 0; h->saved_mode = (Saved)save; h->next_param_stage = 0; }
-    if (save && tp) { h->saved_mode = Saved::Tokens; h->saved_depth = Lrun; h->saved_lnpost = tp->ln_post != 0; }
+    if (save && tp) { h->saved_mode = save == 2 ? Saved::TokensParams : Saved::Tokens; h->saved_depth = Lrun; h->saved_lnpost = tp->ln_post != 0; }
     if (peer) {      // (for the peer's backward only - a provider's single slots / no probabilities kept for a batched backward)
         if (h->provider || !h->own_flash) h->saved_mode = Saved::ForPeer;
         h->exported_to = peer->uid;
@@ -276,7 +276,9 @@ extern "C" int rvlm_vit_forward_tokens(rvlm_vit* h, const float* x, const float*
     RVLM_REQUIRE(h && x && out_tokens, "rvlm_vit_forward_tokens: null argument");
     int rc = tokens_check(h, B, depth, save, "rvlm_vit_forward_tokens"); if (rc) return rc;
     RVLM_REQUIRE(!out_emb || depth == h->L, "rvlm_vit_forward_tokens: the pooled embedding exists at depth == layers only");
-    RVLM_REQUIRE(save == 0 || save == 1, "rvlm_vit_forward_tokens: save must be 0 or 1 (no weight gradients from a token pass)");
+    RVLM_REQUIRE(save == 0 || save == 1 || save == 2, "rvlm_vit_forward_tokens: save must be 0, 1 or 2");
+    RVLM_REQUIRE(save != 2 || h->trainable, "rvlm_vit_forward_tokens: save == 2 needs a trainable handle (no weight gradients from a "
+                                            "token pass of any other handle)");
     if (ln_post && (rc = tok_ensure(h, false))) return rc;
     return vit_forward_tokens(h, x, delta, B, TokPass{depth, ln_post != 0, out_tokens}, save, out_emb, (hipStream_t)stream);
 }

@@ -26,7 +26,9 @@ enum class Saved {
     Params = 2,     // ... and the inputs of every linear layer (trainable handles)
     ForPeer = 3,    // run for another handle's backward (FwdPass::peer): a provider's single slots / no probabilities kept
     Tokens = 4,     // a token pass: saved_depth blocks, every row of the last one, token rows as outputs
+    TokensParams = 5,   // ... and the inputs of every linear layer of those blocks (trainable handles): a superset of Tokens
 };
+static inline bool is_token_pass(Saved m) { return m == Saved::Tokens || m == Saved::TokensParams; }
 
 struct ProfRec { int cls; hipEvent_t a, b; };
 struct ProfAcc { double ms = 0, flops = 0, bytes = 0; int64_t n = 0; };
@@ -123,7 +125,8 @@ struct rvlm_vit {
     bool saved_norm = false;
     // token passes (rvlm_vit_forward_tokens): Saved::Tokens = the saved forward ran `saved_depth` blocks, every row of the last one
     // (no class-token tail), and its outputs were the token rows (ln_post applied or not) - differentiated by
-    // rvlm_vit_backward_input_tokens only.  What only the ln_post form needs is allocated by the first pass that asks for it.
+    // rvlm_vit_backward_input_tokens only; Saved::TokensParams (save = 2) also by rvlm_vit_backward_params_tokens.  What only the
+    // ln_post form needs is allocated by the first pass that asks for it.
     int saved_depth = 0;
     bool saved_lnpost = false;
     float *tok_mean = nullptr, *tok_rstd = nullptr;   // [Mp] statistics of ln_post over every token row
@@ -209,10 +212,11 @@ struct SavedView {
 struct ParamSink { const rvlm_vit_weights* gw; int accumulate, stage_begin, stage_end; };
 
 // Which backward may read which saved forward.  A pooled forward the handle kept for itself (Input, or Params: a superset) is read by
-// the input-gradient backward; only Params by the parameter pass; only a token pass by the token backward; the handoff takes any
-// pooled pass of the fp32-storage handle (its own, or one run for the peer).
+// the input-gradient backward; only Params by the parameter pass; only a token pass (Tokens, or TokensParams: a superset) by the token
+// backward; only TokensParams by the token parameter pass; the handoff takes any pooled pass of the fp32-storage handle (its own, or
+// one run for the peer).
 // (Input is checked by vit_backward for every caller; only rvlm_vit_backward_input can arrive there without a forward of its own.)
-enum class Reader { Input, Params, Tokens, Handoff };
+enum class Reader { Input, Params, Tokens, TokensParams, Handoff };
 int saved_check(const rvlm_vit* h, Reader r, int B, const char* who = "");
 
 static inline bool same_input_size(const rvlm_vit* a, const rvlm_vit* b) { return a->in_h == b->in_h && a->in_w == b->in_w; }
@@ -234,6 +238,7 @@ int tokens_check(const rvlm_vit* h, int B, int depth, int save, const char* who)
 int vit_backward(rvlm_vit* h, const float* d_emb, int B, float* grad_x, hipStream_t s);
 int vit_backward_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int B, float* grad_x, hipStream_t s);
 int vit_backward_params(rvlm_vit* h, const float* d_emb, int B, const ParamSink& sink, hipStream_t s);
+int vit_backward_params_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int B, const ParamSink& sink, hipStream_t s);
 int vit_backward_from(rvlm_vit* hb, rvlm_vit* hx, const float* d_emb, int B, float* grad_x, hipStream_t s);
 // grid of the element-wise kernels (grid-stride loops of 256 threads)
 static inline int ew_blocks(size_t n) { size_t b = (n + 1023) / 1024; if (b > 2048) b = 2048; if (b < 1) b = 1; return (int)b; }

@@ -2,11 +2,13 @@
 // the tokens a VLM reads (llava/model/multimodal_encoder/clip_encoder.py:55-65, open_flamingo/src/flamingo.py:217,242) - into the
 // start of the residual-gradient stream in the form the handle's backward runs on (fp32, fp32 + bf16 copy, or bf16 only).
 //
-// Rules both kernels keep: 16-byte global accesses (8 consecutive columns per thread and step; W is a multiple of 64), trip counts
+// rvlm_tokens_cosine (RVLM_HAS_TOKEN_TRAINING) is the logging metric of the token training step over the same rows.
+//
+// Rules all kernels keep: 16-byte global accesses (8 consecutive columns per thread and step; W is a multiple of 64), trip counts
 // from the shape alone, fixed-order fp32 sums (per-thread partial over a shape-derived index sequence, xor-shuffle tree inside the
 // wave, the four wave partials through LDS summed in wave order, the chunk partials of an image summed in chunk order by one thread):
 // the same input gives the same bits on every run, no float atomics.  A non-finite per-image loss raises
-// RVLM_FLAG_TOKENS_NONFINITE; nothing in either kernel branches or loops on a data value.
+// RVLM_FLAG_TOKENS_NONFINITE; nothing in any kernel branches or loops on a data value.
 #include "kernels.h"
 
 namespace rvlm {
@@ -125,6 +127,60 @@ tokens_l2_finish_kernel(const float* __restrict__ partial, int B, int nch, int m
     }
 }
 
+// Row cosine of the selected token rows (rows s >= first meet row s - first of ref [B, S - first, W]), F.cosine_similarity's epsilon
+// rule as in cosine_rows_kernel (loss_kernels.hip): a.b / sqrt(max(|a|^2 |b|^2, 1e-16)).  One workgroup per (image, chunk of TOK_ROWS
+// rows): wave w takes rows 2w and 2w + 1 of the chunk, lane i the 8-column groups i, i + 64, ...; partial[block] = the chunk's
+// cosines summed wave by wave, row by row (unselected rows and rows past S add an exact 0).
+__global__ void __launch_bounds__(256)
+tokens_cosine_kernel(const float* __restrict__ t, const float* __restrict__ ref, int S, int W, int first,
+                     float* __restrict__ partial) {
+    __shared__ float wsum[4];
+    const int W8 = W >> 3, nch = (S + TOK_ROWS - 1) / TOK_ROWS;
+    const int b = blockIdx.x / nch, s0 = (blockIdx.x % nch) * TOK_ROWS;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int nsel = S - first;
+    float acc = 0.0f;
+#pragma unroll
+    for (int j = 0; j < TOK_ROWS / 4; ++j) {
+        const int sr = s0 + wave * (TOK_ROWS / 4) + j;
+        const bool live = sr >= first && sr < S;      // (uniform over the wave)
+        float ab = 0.0f, aa = 0.0f, bb = 0.0f;
+        if (live) {
+            const float* pa = t + ((long)b * S + sr) * W;
+            const float* pb = ref + ((long)b * nsel + (sr - first)) * W;
+            for (int g = lane; g < W8; g += 64) {
+                float x[8], y[8];
+                tok_load8(pa + (g << 3), x);
+                tok_load8(pb + (g << 3), y);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { ab = fmaf(x[e], y[e], ab); aa = fmaf(x[e], x[e], aa); bb = fmaf(y[e], y[e], bb); }
+            }
+        }
+        ab = wave_sum(ab); aa = wave_sum(aa); bb = wave_sum(bb);
+        acc += live ? ab / sqrtf(fmaxf(aa * bb, 1e-16f)) : 0.0f;
+    }
+    if (lane == 0) wsum[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+// second stage: per_image[b] = (the image's chunk partials in chunk order) / rows; mean = (their sum in image order) / B.  The few
+// terms of these two sums are added in double: a mean of O(1) cosines over hundreds of rows keeps its seventh digit.
+__global__ void __launch_bounds__(256)
+tokens_cosine_finish_kernel(const float* __restrict__ partial, int B, int nch, int rows, float* __restrict__ per_image,
+                            float* __restrict__ mean) {
+    for (int b = threadIdx.x; b < B; b += 256) {
+        double a = 0.0;
+        for (int j = 0; j < nch; ++j) a += (double)partial[(long)b * nch + j];
+        per_image[b] = (float)(a / (double)rows);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && mean) {
+        double a = 0.0;
+        for (int b = 0; b < B; ++b) a += (double)per_image[b];
+        *mean = (float)(a / (double)B);
+    }
+}
+
 static inline bool aligned16(const void* p) { return ((size_t)p & 15) == 0; }
 
 int tokens_seed(const float* d_tok, const float* cls_add, long ld_cls, float* d32, bf16_t* dlp, int M, int Mp, int S, int W,
@@ -172,4 +228,21 @@ extern "C" int rvlm_tokens_l2_loss_grad(const float* tokens, const float* ref_to
                                         float* loss_scalar, float* scratch, int32_t* flags, rvlm_stream_t stream) {
     return tokens_l2_loss_grad(tokens, ref_tokens, B, S, W, select, reduction, seed_f32, (bf16_t*)seed_bf16, seed_rows, loss_per_sample,
                                loss_scalar, scratch, flags, (hipStream_t)stream);
+}
+
+extern "C" int rvlm_tokens_cosine(const float* tokens, const float* ref_tokens, int B, int S, int W, int select, float* out_per_image,
+                                  float* out_mean, float* scratch, rvlm_stream_t stream) {
+    RVLM_REQUIRE(tokens && ref_tokens && out_per_image && scratch, "rvlm_tokens_cosine: null argument");
+    RVLM_REQUIRE(B > 0 && S > 1 && W > 0 && W % 8 == 0, "rvlm_tokens_cosine: need B > 0, S > 1 and a width that is a multiple of 8");
+    RVLM_REQUIRE(select == RVLM_TOKENS_ALL || select == RVLM_TOKENS_PATCH, "rvlm_tokens_cosine: unknown select");
+    RVLM_REQUIRE((long)B * S < (1L << 31) / TOK_ROWS, "rvlm_tokens_cosine: too many rows");
+    RVLM_REQUIRE(aligned16(tokens) && aligned16(ref_tokens), "rvlm_tokens_cosine: pointers must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int nch = cdiv(S, TOK_ROWS), first = select == RVLM_TOKENS_PATCH ? 1 : 0;
+    hipLaunchKernelGGL(tokens_cosine_kernel, dim3(B * nch), dim3(256), 0, s, tokens, ref_tokens, S, W, first, scratch);
+    RVLM_CHECK_LAUNCH();
+    hipLaunchKernelGGL(tokens_cosine_finish_kernel, dim3(1), dim3(256), 0, s, (const float*)scratch, B, nch, S - first,
+                       out_per_image, out_mean);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
 }

@@ -297,7 +297,8 @@ class VitEngine:
     def forward_tokens(self, x, delta=None, depth=None, ln_post=False, save=False, return_emb=False):
         """The residual stream after ``depth`` resblocks, ``[B, S, W]`` with the class row first (rvlm_vit_forward_tokens):
         ``depth = layers - 1`` (or -2) is LLaVA's tower, ``layers`` (None, -1) what open_clip returns with ``output_tokens``.
-        ``ln_post`` normalises every row first.  ``return_emb`` (full depth only) also returns the pooled embedding."""
+        ``ln_post`` normalises every row first.  ``return_emb`` (full depth only) also returns the pooled embedding.
+        ``save=2`` (trainable engines) also keeps what ``backward_params_tokens`` needs."""
         h = self._token_handle("forward_tokens")
         self._check_images(x)
         x = _f32c(x)
@@ -309,14 +310,13 @@ class VitEngine:
         tok = torch.empty(B, self.n_tokens, self.cfg.width, device=x.device, dtype=torch.float32)
         emb = torch.empty(B, self.cfg.out_dim, device=x.device, dtype=torch.float32) if return_emb else None
         with torch.cuda.device(x.device):
-            L.check(self.lib.rvlm_vit_forward_tokens(h, x.data_ptr(), L.ptr(d), B, depth, int(bool(ln_post)), int(bool(save)),
+            sv = 2 if (not isinstance(save, bool) and save == 2) else int(bool(save))
+            L.check(self.lib.rvlm_vit_forward_tokens(h, x.data_ptr(), L.ptr(d), B, depth, int(bool(ln_post)), sv,
                                                      tok.data_ptr(), L.ptr(emb), L.stream_ptr()), "rvlm_vit_forward_tokens")
         self.generation += 1
         return (tok, emb) if return_emb else tok
 
-    def backward_input_tokens(self, d_tokens, d_emb=None) -> torch.Tensor:
-        """Input gradient of ``<d_tokens, tokens> (+ <d_emb, emb>)`` of the last ``forward_tokens(..., save=True)``."""
-        h = self._token_handle("backward_input_tokens")
+    def _token_cotangents(self, d_tokens, d_emb):
         _require_cuda(d_tokens, "d_tokens")
         dt = _f32c(d_tokens)
         if dt.dim() != 3 or tuple(dt.shape[1:]) != (self.n_tokens, self.cfg.width):
@@ -328,6 +328,30 @@ class VitEngine:
             de = _f32c(d_emb)
             if tuple(de.shape) != (B, self.cfg.out_dim):
                 raise ValueError(f"expected a [{B},{self.cfg.out_dim}] embedding cotangent, got {tuple(de.shape)}")
+        return dt, de, B
+
+    def backward_params_tokens(self, d_tokens, grads: dict, d_emb=None, accumulate: bool = False, stages=None):
+        """Weight gradients of ``<d_tokens, tokens> (+ <d_emb, emb>)`` of the last ``forward_tokens(..., save=2)`` into the fp32
+        tensors of ``grads`` (rvlm_vit_backward_params_tokens).  Parameters the cotangent cannot reach (blocks >= depth; ``proj``
+        without ``d_emb``; ``ln_post.*`` without ``ln_post`` or ``d_emb``) are zero-filled, or left alone with ``accumulate``.
+        ``stages=(begin, end)``: that slice of the pass, as in ``backward_params``."""
+        h = self._token_handle("backward_params_tokens")
+        dt, de, B = self._token_cotangents(d_tokens, d_emb)
+        with torch.cuda.device(dt.device):
+            w, keep = self._weights_struct(grads, inplace=True)
+            if stages is None:
+                L.check(self.lib.rvlm_vit_backward_params_tokens(h, dt.data_ptr(), L.ptr(de), B, C.byref(w), int(bool(accumulate)),
+                                                                 L.stream_ptr()), "rvlm_vit_backward_params_tokens")
+            else:
+                L.check(self.lib.rvlm_vit_backward_params_tokens_stages(h, dt.data_ptr(), L.ptr(de), B, C.byref(w),
+                                                                        int(bool(accumulate)), int(stages[0]), int(stages[1]),
+                                                                        L.stream_ptr()), "rvlm_vit_backward_params_tokens_stages")
+        del keep
+
+    def backward_input_tokens(self, d_tokens, d_emb=None) -> torch.Tensor:
+        """Input gradient of ``<d_tokens, tokens> (+ <d_emb, emb>)`` of the last ``forward_tokens(..., save=True)``."""
+        h = self._token_handle("backward_input_tokens")
+        dt, de, B = self._token_cotangents(d_tokens, d_emb)
         g = torch.empty(B, 3, *self.input_size, device=dt.device, dtype=torch.float32)
         with torch.cuda.device(dt.device):
             L.check(self.lib.rvlm_vit_backward_input_tokens(h, dt.data_ptr(), L.ptr(de), B, g.data_ptr(), L.stream_ptr()),

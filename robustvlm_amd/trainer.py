@@ -20,6 +20,11 @@ inside ``backward``; here every rank owns one GPU and its shard of the batch, th
 the gradient all-reduce (RCCL through torch.distributed) runs in ``n_buckets`` contiguous slices of ONE flat fp32
 buffer, each launched as soon as the backward stages that fill it are done, so that it overlaps the remaining stages
 (rvlm_vit_backward_params_stages); the 1/world_size scaling is fused into the optimizer kernel.
+
+``loss="l2-tokens"`` trains on what a VLM reads from the tower instead of the pooled embedding: the same step with the token
+passes (``forward_tokens`` / ``pgd_run_tokens`` / ``backward_params_tokens``) at ``token_depth`` over ``token_select`` rows,
+loss ``mean_b sum_{rows, W} (tokens - ref)^2``.  Parameters the token loss cannot reach (the blocks above ``token_depth``,
+``ln_post``, ``proj``) are left alone by the optimizer, as torch leaves parameters whose ``grad`` is None.
 """
 from __future__ import annotations
 
@@ -30,10 +35,11 @@ import torch.distributed as dist
 
 from . import _lib as L
 from .clip_model import ClipVisionModel, ComputeLossWrapper, compute_loss
-from .config import state_dict_shapes, backward_stage_keys, parameter_order
+from .config import CONFIGS, state_dict_shapes, backward_stage_keys, parameter_order
+from .attack_utils import LINF
 from .dist import allreduce_sum_span
 from .engine import VitEngine
-from .pgd_train import pgd
+from .pgd_train import pgd, _raise_from_flags
 from .apgd_train import apgd_train
 
 
@@ -107,9 +113,12 @@ class AdversarialTrainer:
                  iterations_adv=10, stepsize_adv=1 / 255, output_normalize=False, clean_weight=0.0,
                  embedding_text_labels_norm=None, betas=(0.9, 0.999), adam_eps=1e-8, device=None,
                  loss_clean="l2", trades=False, n_buckets=4, metrics=True, process_group=None,
-                 always_reduce=False, opt="adamw", momentum_sgd=0.9):
+                 always_reduce=False, opt="adamw", momentum_sgd=0.9, token_depth=-2, token_select="patch"):
         if opt not in ("adamw", "sgd"):                           # …clip.py:196-206; before any device work
             raise ValueError(f"Optimizer {opt} not supported.")
+        self.token_mode = loss == "l2-tokens"
+        self.token_depth, self.token_select = self._check_token_options(
+            cfg, loss, inner_loss, loss_clean, attack, clean_weight, output_normalize, token_depth, token_select)
         self.opt, self.momentum_sgd = opt, float(momentum_sgd)
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.cfg = cfg
@@ -150,9 +159,44 @@ class AdversarialTrainer:
         # handles and the stream ordering on a single GPU; the reduction itself is then the identity)
         self._reduce = self.world > 1 or (bool(always_reduce) and dist.is_available() and dist.is_initialized())
         self.buckets = bucket_plan(self.engine.n_stages, n_buckets if self._reduce else 1)
+        if self.token_mode:
+            # stages [0, first): the seed of the residual-gradient stream and parameters the token loss cannot reach - nothing to
+            # reduce, nothing for the optimizer; the buckets are planned over the reached stages [first, n_stages)
+            first = 1 + cfg.layers - self.token_depth
+            self._token_first_stage = first
+            self._token_buckets = [(first + a, first + b) for a, b in
+                                   bucket_plan(self.engine.n_stages - first, n_buckets if self._reduce else 1)]
+            self._token_span_lo = self.params.stage_offsets[first]
         # a backend without device collectives (gloo in the CPU/1-GPU tests) reduces through a pinned host copy
         self._device_collectives = self._reduce and dist.get_backend(self.pg) == "nccl"
         self._checked_global_batch = False
+
+    @staticmethod
+    def _check_token_options(cfg, loss, inner_loss, loss_clean, attack, clean_weight, output_normalize, token_depth, token_select):
+        """The refusals of the token loss, raised before any device work.  Returns (depth in 1..layers, select)."""
+        if loss != "l2-tokens":
+            if "l2-tokens" in (inner_loss, loss_clean):
+                raise ValueError("inner_loss / loss_clean 'l2-tokens' go with loss='l2-tokens' (no joint pooled + token loss)")
+            return None, token_select
+        if attack == "apgd":
+            raise ValueError("loss='l2-tokens': attack 'apgd' not supported (no batched token APGD); use 'pgd' or 'none'")
+        if attack not in ("pgd", "none"):
+            raise ValueError(f"attack {attack} not supported")
+        if attack != "none" and inner_loss != "l2-tokens":
+            raise ValueError(f"loss='l2-tokens' attacks the tokens it trains on: inner_loss must be 'l2-tokens', got {inner_loss!r}")
+        if clean_weight > 0 and loss_clean != "l2-tokens":
+            raise ValueError(f"loss='l2-tokens' with clean_weight > 0 needs loss_clean='l2-tokens', got {loss_clean!r}")
+        if output_normalize:
+            raise ValueError("loss='l2-tokens': output_normalize applies to the pooled embedding, not to token rows")
+        if token_select not in ("all", "patch"):
+            raise ValueError(f"token_select {token_select!r}: 'all' or 'patch'")
+        layers = (CONFIGS[cfg] if isinstance(cfg, str) else cfg).layers
+        d = int(token_depth)
+        if d <= 0:                                                # LLaVA's select_layer convention, as VitEngine._depth
+            d = layers + 1 + d
+        if not 1 <= d <= layers:
+            raise ValueError(f"token_depth {token_depth!r} outside 1..{layers} (or -{layers}..-1)")
+        return d, token_select
 
     # -- pieces of the step ----------------------------------------------------------------------
     def _attack(self, data, targets, e0):
@@ -228,22 +272,119 @@ class AdversarialTrainer:
         dist.all_reduce(n, op=dist.ReduceOp.SUM, group=self.pg)
         return n_local * self.world / float(n.item())
 
-    def _optimizer_step(self):
+    def _optimizer_step(self, lo: int = 0):
         """optimizer.step() (…clip.py:362) over the flat buffers at ``cur_lr``; the 1 / world of the summed gradients
-        goes in as grad_scale."""
+        goes in as grad_scale.  ``lo``: the step runs on the span [lo, numel) of every buffer only (a multiple of 4 floats:
+        the span stays 16-byte aligned) - what lies below is neither decayed nor moved, and its moments stay as they are."""
+        n = self.params.numel - lo
+
+        def at(t):
+            return None if t is None else t.data_ptr() + 4 * lo
         with torch.cuda.device(self.device):
             if self.opt == "sgd":
-                L.check(self.lib.rvlm_sgd_step(self.params.flat.data_ptr(), self.grads.flat.data_ptr(),
-                                               L.ptr(self.momentum_buffer), self.params.numel, float(self.cur_lr),
+                L.check(self.lib.rvlm_sgd_step(at(self.params.flat), at(self.grads.flat),
+                                               at(self.momentum_buffer), n, float(self.cur_lr),
                                                self.momentum_sgd, self.wd, int(self._sgd_first), 1.0 / self.world,
                                                L.stream_ptr()), "rvlm_sgd_step")
                 self._sgd_first = False
                 return
             b1, b2 = self.betas
-            L.check(self.lib.rvlm_adamw_step(self.params.flat.data_ptr(), self.grads.flat.data_ptr(),
-                                             self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), self.params.numel,
+            L.check(self.lib.rvlm_adamw_step(at(self.params.flat), at(self.grads.flat),
+                                             at(self.exp_avg), at(self.exp_avg_sq), n,
                                              float(self.cur_lr), b1, b2, self.adam_eps, self.wd, self.step_total,
                                              1.0 / self.world, L.stream_ptr()), "rvlm_adamw_step")
+
+    # -- the token step (loss="l2-tokens") --------------------------------------------------------------------------
+    def _select_rows(self, tokens):
+        return tokens[:, 1:] if self.token_select == "patch" else tokens
+
+    def _attack_tokens(self, data, ref_tokens):
+        """The inner attack on the tokens: pgd() from the pooled trainer's random start (rvlm_pgd_run_tokens)."""
+        if self.attack == "none":
+            return data
+        d0 = torch.zeros_like(data).uniform_(-self.eps, self.eps)
+        adv, flags, _ = self.engine.pgd_run_tokens(data, d0, ref_tokens, self.eps, self.iterations_adv, self.stepsize_adv, 0.9,
+                                                   "max", depth=self.token_depth, ln_post=False, select=self.token_select,
+                                                   reduction="mean", norm_kind=0 if self.norm in LINF else 2)
+        flags = int(flags.item())
+        assert not (flags & L.FLAG_TOKENS_NONFINITE), "non-finite token loss"
+        _raise_from_flags(flags)
+        return adv
+
+    def _tokens_loss_backward(self, x, ref_tokens, weight, accumulate, reduce_grads):
+        """Token forward (activations kept for wgrad) + mean_b sum (tokens - ref)^2 and its seed in one kernel + weight gradients
+        scaled by ``weight``; with ``reduce_grads`` the buckets of the reached stages are all-reduced under the later ones."""
+        eng = self.engine
+        tok = eng.forward_tokens(x, depth=self.token_depth, ln_post=False, save=2)
+        B, S, W = tok.shape
+        ref, sel = eng._token_ref(ref_tokens, B, self.token_select)
+        seed = torch.empty_like(tok)
+        per = torch.empty(B, dtype=torch.float32, device=tok.device)
+        loss = torch.empty(1, dtype=torch.float32, device=tok.device)
+        scratch = torch.empty(B * ((S + 7) // 8), dtype=torch.float32, device=tok.device)
+        with torch.cuda.device(tok.device):
+            L.check(self.lib.rvlm_tokens_l2_loss_grad(tok.data_ptr(), ref.data_ptr(), B, S, W, sel, L.RED_MEAN, seed.data_ptr(), None,
+                                                      0, per.data_ptr(), loss.data_ptr(), scratch.data_ptr(), None,
+                                                      L.stream_ptr()), "rvlm_tokens_l2_loss_grad")
+        if weight != 1.0:
+            seed *= weight
+        if not reduce_grads:
+            eng.backward_params_tokens(seed, self.grads.views, accumulate=accumulate)
+            return loss.reshape(()), tok
+        eng.backward_params_tokens(seed, self.grads.views, accumulate=accumulate, stages=(0, self._token_first_stage))
+        works = []
+        for a, b in self._token_buckets:
+            eng.backward_params_tokens(seed, self.grads.views, accumulate=accumulate, stages=(a, b))
+            works.append(self._allreduce_span(*self.params.stage_span(a, b)))   # async: overlaps the next stages
+        for w in works:
+            if w is not None:
+                w.wait()
+        return loss.reshape(()), tok
+
+    @torch.no_grad()
+    def _tokens_cos_mean(self, tokens, ref_tokens):
+        """Mean over the batch of the mean row cosine between ``tokens`` [B, S, W] and the selected-row reference
+        (rvlm_tokens_cosine): the token form of ``_cos_mean``."""
+        B, S, W = tokens.shape
+        ref, sel = self.engine._token_ref(ref_tokens, B, self.token_select)
+        per = torch.empty(B, dtype=torch.float32, device=tokens.device)
+        mean = torch.empty(1, dtype=torch.float32, device=tokens.device)
+        scratch = torch.empty(B * ((S + 7) // 8), dtype=torch.float32, device=tokens.device)
+        with torch.cuda.device(tokens.device):
+            L.check(self.lib.rvlm_tokens_cosine(tokens.data_ptr(), ref.data_ptr(), B, S, W, sel, per.data_ptr(), mean.data_ptr(),
+                                                scratch.data_ptr(), L.stream_ptr()), "rvlm_tokens_cosine")
+        return mean.reshape(())
+
+    def _train_step_tokens(self, data, data_adv, global_batch, global_metrics):
+        with torch.no_grad():
+            ref0 = self._select_rows(self.engine_orig.forward_tokens(data, depth=self.token_depth)).contiguous()
+        if data_adv is None:
+            data_adv = self._attack_tokens(data, ref0)
+        cw = self.clean_weight
+        wshard = self._shard_weight(data.shape[0], global_batch)
+        loss_clean = torch.zeros((), device=self.device)
+        tok_clean = None
+        accumulate = False
+        if cw > 0.:
+            loss_clean, tok_clean = self._tokens_loss_backward(data, ref0, cw * wshard, False, False)
+            accumulate = True
+        elif self.metrics or self.trades:
+            tok_clean = self.engine.forward_tokens(data, depth=self.token_depth, save=False)
+        ref = self._select_rows(tok_clean).contiguous() if self.trades else ref0
+        loss, tok_adv = self._tokens_loss_backward(data_adv, ref, (1.0 - cw) * wshard, accumulate, self._reduce)
+        self.step_total += 1
+        self._optimizer_step(self._token_span_lo)
+        self.engine.load_state_dict(self.params.views)
+        lr_used = self.cur_lr
+        self.cur_lr = cosine_lr_value(self.step_total, self.lr, self.warmup, self.steps)
+        out = dict(loss=loss, loss_clean=loss_clean, loss_total=cw * loss_clean + (1 - cw) * loss, lr=lr_used)
+        if self.metrics:
+            out["cos_sim_clean"] = self._tokens_cos_mean(tok_clean, ref0)
+            out["cos_sim"] = self._tokens_cos_mean(tok_adv, ref0)
+            out["racc"] = out["acc"] = None
+        if global_metrics and self.world > 1:
+            out = self._global_means(out, data.shape[0])
+        return out
 
     @torch.no_grad()
     def _cos_mean(self, a, b):
@@ -298,7 +439,11 @@ class AdversarialTrainer:
         precomputed adversarial images (tests).  ``global_batch`` (optional): the number of images all ranks hold in
         this step, when the caller knows it (equal shards: world * len(data)) - skips the size all-reduce.  The
         returned loss / metrics are this rank's SHARD values; ``global_metrics=True`` (one extra 8-number all-reduce and
-        a host sync, for logging steps) returns them over the global batch like the reference's DataParallel logs."""
+        a host sync, for logging steps) returns them over the global batch like the reference's DataParallel logs.
+        With ``loss="l2-tokens"`` the same step runs on the tokens: cos_sim / cos_sim_clean are mean row cosines of the trained
+        model's tokens against the frozen model's (rvlm_tokens_cosine), acc / racc are None."""
+        if self.token_mode:
+            return self._train_step_tokens(data, data_adv, global_batch, global_metrics)
         with torch.no_grad():
             e0 = self.model_orig(data, self.output_normalize)                   # …clip.py:296-297
         if data_adv is None:
@@ -415,7 +560,9 @@ class AdversarialTrainer:
         """``torch.optim.AdamW(visual.parameters()).state_dict()`` layout (…clip.py:196-197,240,471), or
         ``torch.optim.SGD``'s for ``opt="sgd"``: 'state' keyed by the positional index of ``visual.parameters()``, one
         param group - a reference run can resume from it and vice versa.  'param_names' (index -> key) is added for
-        readers without the module (torch ignores it)."""
+        readers without the module (torch ignores it).  One difference from torch's file, with ``loss="l2-tokens"`` only:
+        torch writes no entry for a parameter that never had a gradient; here every parameter has one, with zero moments
+        for those the token loss never reaches (loading such a file and resuming gives the same steps)."""
         order = parameter_order(self.cfg)
 
         def piece(flat, k):
