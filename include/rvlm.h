@@ -244,6 +244,9 @@ int rvlm_sgd_step(float* params, const float* grads, float* momentum_buf, size_t
  *        rvlm_vit_fwd_inputgrad, dg (grad_x) without an autograd graph.
  * pred_eq (optional, u8[B]) = argmax_c(logits) == targets (head losses only).  scratch: the head losses need
  * B*C + D*C floats (may be NULL for L2).  y_target: DLR_TARGETED and LOGIT_DIFF (else NULL).
+ * Caller's duty: every targets[b] and y_target[b] lies in [0, C).  The labels live on the device, so this call cannot
+ * check them without a sync; a label outside the range makes the kernel read logits[b][label] outside the row.
+ * (The Python callers check before they launch and raise IndexError, as F.cross_entropy does.)
  * ------------------------------------------------------------------------------------------- */
 int rvlm_loss_grad(int loss_kind, int reduction, const float* emb, const float* ref,
                    const int64_t* targets, const int64_t* y_target, int B, int D, int C, float logit_scale,

@@ -185,6 +185,8 @@ class _LossFn(torch.autograd.Function):
         d_emb = torch.empty_like(e)
         scratch = torch.empty(B * Ccls + D * Ccls, dtype=torch.float32, device=e.device) if Ccls else None
         tg = targets.detach().to(torch.int64).contiguous() if kind == L.LOSS_CE else None
+        if tg is not None and tg.numel() and (int(tg.min()) < 0 or int(tg.max()) >= Ccls):
+            raise IndexError(f"Target out of bounds for {Ccls} classes")           # F.cross_entropy's check
         with torch.cuda.device(e.device):
             L.check(lib.rvlm_loss_grad(kind, reduction, e.data_ptr(), r.data_ptr(), L.ptr(tg), None, B, D, Ccls,
                                        float(logit_scale), per.data_ptr(), scalar.data_ptr(),

@@ -34,7 +34,7 @@ ce_loss_kernel(float* __restrict__ logits, const int64_t* __restrict__ targets, 
     int mi = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
         const float v = l[c];
-        if (v > m) { m = v; mi = c; }
+        if (v > m || (v == m && c < mi)) { m = v; mi = c; }     // the second clause: a leading -inf keeps its index
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -62,6 +62,9 @@ ce_loss_kernel(float* __restrict__ logits, const int64_t* __restrict__ targets, 
 // top-4 selection (4 rounds of wave arg-max over per-lane candidates), the loss with the reference's operation order,
 // and d loss / d logits written in place (autograd of the same expression: the sort routes gradient to the elements
 // holding ranks 1, 3 (and 4 / 2)).  pred_eq = (arg-max == y).
+// The gradient divides twice, (num / den) / den as torch's backward of a division does, and the targeted form takes its
+// denominator from the differences to the top logit: z_(3) + z_(4) rounds at the logits' magnitude, which the small den of
+// crowded classes (C = 1000) does not forgive.  The value keeps the reference's order and stays bit-equal to it.
 __global__ void __launch_bounds__(256)
 dlr_loss_kernel(float* __restrict__ logits, const int64_t* __restrict__ targets, const int64_t* __restrict__ y_target,
                 int B, int C, float gscale, float* __restrict__ per_sample, uint8_t* __restrict__ pred_eq,
@@ -112,12 +115,13 @@ dlr_loss_kernel(float* __restrict__ logits, const int64_t* __restrict__ targets,
         const float ind = (zi[0] == y) ? 1.0f : 0.0f;
         num = -((zy - z[1] * ind) - z[0] * (1.0f - ind));
         den = (z[0] - z[2]) + 1e-12f;
-        const float gn = 1.0f / den, gd = -num / (den * den);
+        const float gn = 1.0f / den, gd = -(num / den) / den;
         g_y = -gn; g_2 = ind * gn; g_1 = (1.0f - ind) * gn + gd; g_3 = -gd;
     } else {
         num = -(zy - l[yt]);
         den = (z[0] - 0.5f * (z[2] + z[3])) + 1e-12f;
-        const float gn = 1.0f / den, gd = -num / (den * den);
+        const float dg = 0.5f * ((z[0] - z[2]) + (z[0] - z[3])) + 1e-12f;
+        const float gn = 1.0f / dg, gd = -(num / dg) / dg;
         g_y = -gn; g_t = gn; g_1 = gd; g_3 = -0.5f * gd; g_4 = -0.5f * gd;
     }
     if (lane == 0) {
@@ -151,7 +155,7 @@ logit_diff_kernel(float* __restrict__ logits, const int64_t* __restrict__ target
     int mi = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
         const float v = l[c];
-        if (v > m) { m = v; mi = c; }
+        if (v > m || (v == m && c < mi)) { m = v; mi = c; }     // the second clause: a leading -inf keeps its index
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -191,7 +195,7 @@ argmax_eq_kernel(const float* __restrict__ logits, const int64_t* __restrict__ t
     int mi = 0x7fffffff;
     for (int c = lane; c < C; c += 64) {
         const float v = l[c];
-        if (v > m) { m = v; mi = c; }
+        if (v > m || (v == m && c < mi)) { m = v; mi = c; }     // the second clause: a leading -inf keeps its index
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
