@@ -48,6 +48,8 @@ extern "C" {
 /* RVLM_HAS_TOKEN_TRAINING: weight gradients through the token door - rvlm_vit_forward_tokens(save = 2),
  * rvlm_vit_backward_params_tokens(_stages), rvlm_tokens_cosine */
 #define RVLM_HAS_TOKEN_TRAINING 1
+/* RVLM_HAS_TOKEN_APGD: rvlm_apgd_run_tokens - vlm_eval/attacks/apgd.py's loop on the per-image token loss, batched, device resident */
+#define RVLM_HAS_TOKEN_APGD 1
 
 typedef void* rvlm_stream_t; /* hipStream_t */
 typedef struct rvlm_vit rvlm_vit;
@@ -402,6 +404,7 @@ int rvlm_fab_jacobian_argmin(const float* g_k, const float* g_y, const float* df
  *   pgd()        train/pgd_train.py:5-68          -> rvlm_pgd_run
  *   apgd_train() train/apgd_train.py:125-373      -> rvlm_apgd_run (train_variant = 1)
  *   APGDAttack.attack_single_run autopgd_base.py:205-451 -> rvlm_apgd_run (train_variant = 0)
+ *   apgd()       vlm_eval/attacks/apgd.py:163-368 on the token loss, per image -> rvlm_apgd_run_tokens (RVLM_HAS_TOKEN_APGD)
  * with the FARE / TeCoA losses bound (ComputeLossWrapper, …clip.py:260-274).
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
@@ -516,6 +519,24 @@ int rvlm_vit_tokens_fwd_inputgrad(rvlm_vit* h, const float* x, const float* delt
 int rvlm_pgd_run_tokens(rvlm_vit* h, const float* x, const float* delta0, int B, int depth, int ln_post, int select,
                         const float* ref_tokens, int reduction, int norm_kind, float eps, int iterations, float stepsize,
                         float momentum, int mode_max, float* x_adv_out, float* loss_trace, int32_t* flags, rvlm_stream_t stream);
+
+/* apgd() of vlm_eval/attacks/apgd.py:163-368 (L-inf and L2 branches, mask = None, maximising) with the token loss as the model, run
+ * independently for every image of the batch (RVLM_HAS_TOKEN_APGD).  The per-image loss is the RVLM_RED_NONE form of
+ * rvlm_tokens_l2_loss_grad - sum over the selected rows and W of (tokens - ref_tokens)^2, seed 2 (t - ref) without a 1 / B.
+ * Start: clamp(x_init ? x_init : x, 0, 1), forward + backward.  Each of the n_iter (1..1024) iterations: rvlm_apgd_linf_step /
+ * rvlm_apgd_l2_step (a = 1.0 at i == 0, else 0.75), forward + loss, backward unless i == n_iter - 1 (:300-304),
+ * rvlm_apgd_controller_rho with an all-zero `pred` (as rvlm_apgd_masked_bookkeeping: x_best_adv follows the last iterate, :310) and
+ * the oscillation threshold `rho` (the reference: 0.75), rvlm_apgd_select.  The checkpoint schedule is the host's; nothing is read
+ * back or allocated, the state lives in the handle's attack buffers.  step0 = alpha * eps (the reference: alpha = 2).
+ * Outputs: x_best_out [B, 3, in_h, in_w] (required) / loss_best_out [B] = the iterate of highest loss and that loss; x_last_out
+ * (optional) = the reference's third return value x_best_adv; loss_trace_out (optional, [n_iter + 1, B]): row 0 the start point's
+ * loss, row i + 1 the loss after iteration i; step_out (optional, [B]) the final step sizes.  flags (optional): RVLM_FLAG_NAN_GRAD
+ * from the steps, RVLM_FLAG_TOKENS_NONFINITE from the loss.  norm_kind other than 0 / 2: RVLM_ERR_UNSUPPORTED; depth, select, B,
+ * handle kind and scratch size are refused as by rvlm_pgd_run_tokens.  Leaves a saved token pass, like every token loop. */
+int rvlm_apgd_run_tokens(rvlm_vit* h, const float* x, const float* x_init, int B, int depth, int ln_post, int select,
+                         const float* ref_tokens, int norm_kind, float eps, int n_iter, float step0, float rho, float* x_best_out,
+                         float* loss_best_out, float* x_last_out, float* loss_trace_out, float* step_out, int32_t* flags,
+                         rvlm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * VLM-side attacks (RVLM_HAS_VLM_ATTACKS): the arithmetic of one iteration of vlm_eval/attacks/pgd.py (class PGD) and apgd.py
@@ -699,7 +720,8 @@ int rvlm_version(void);   /* = RVLM_VERSION.  101: rvlm_loss_spec.y_target, rvlm
                            * rvlm_square_l2_propose, RVLM_FLAG_SQUARE_NONFINITE (announced by RVLM_HAS_SQUARE_L2);
                            * rvlm_sgd_step (announced by RVLM_HAS_SGD);
                            * rvlm_vit_forward_tokens(save = 2), rvlm_vit_backward_params_tokens(_stages), rvlm_tokens_cosine
-                           * (announced by RVLM_HAS_TOKEN_TRAINING) */
+                           * (announced by RVLM_HAS_TOKEN_TRAINING);
+                           * rvlm_apgd_run_tokens (announced by RVLM_HAS_TOKEN_APGD) */
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ arithmetic op runs in the in-tree HIP library ``librvlm.so`` (include/rvlm.h):
     open_clip CLIP.encode_text (third party)            robustvlm_amd.{TextEngine,ClipTextModel}
     CLIP_eval/eval_utils.py::get_text_embeddings        robustvlm_amd.get_text_embeddings
     vlm_eval/attacks/pgd.py::PGD, apgd.py::APGD, apgd   robustvlm_amd.vlm_attacks.{PGD,APGD,apgd}  (+ TokenLossModel)
+    apgd.py::apgd on the token loss, batched            robustvlm_amd.apgd_tokens
 """
 from .config import (VitConfig, CONFIGS, CLIP_MEAN, CLIP_STD, random_state_dict, state_dict_shapes, TextConfig, TEXT_CONFIGS,
                      text_state_dict_shapes, random_text_state_dict)
@@ -33,6 +34,7 @@ from .square import SquareAttack
 from .fab import FABAttack
 from . import vlm_attacks
 from .vlm_attacks import TokenLossModel
+from .token_attacks import apgd_tokens
 from .eval_utils import compute_accuracy_no_dataloader, zeroshot_head, get_text_embeddings, get_text_embeddings_ensemble
 from .preprocess import ResizeCenterCropToTensor
 from .resize import BicubicResize
@@ -43,4 +45,4 @@ __all__ = ["VitConfig", "CONFIGS", "CLIP_MEAN", "CLIP_STD", "random_state_dict",
            "l2", "ce", "compute_acc", "project_perturbation", "normalize_grad", "pgd", "apgd_train",
            "APGDAttack", "APGDAttack_targeted", "AutoAttack", "EvaluationState", "SquareAttack", "FABAttack", "compute_accuracy_no_dataloader", "zeroshot_head", "ResizeCenterCropToTensor", "load_visual_state_dict", "CheckpointWriter", "resume_paths",
            "TextConfig", "TEXT_CONFIGS", "text_state_dict_shapes", "random_text_state_dict", "TextEngine", "ClipTextModel",
-           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict", "BicubicResize", "ClipVisionTower", "vlm_attacks", "TokenLossModel"]
+           "get_text_embeddings", "get_text_embeddings_ensemble", "load_text_state_dict", "BicubicResize", "ClipVisionTower", "vlm_attacks", "TokenLossModel", "apgd_tokens"]

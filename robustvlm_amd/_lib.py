@@ -327,6 +327,11 @@ _SIGS.update({
                                                          C.c_int, C.c_int, c_stream]),
     "rvlm_tokens_cosine": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_stream]),
 })
+_SIGS.update({
+    # apgd() on the per-image token loss as one device loop (csrc/engine_attacks.hip; RVLM_HAS_TOKEN_APGD)
+    "rvlm_apgd_run_tokens": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_float,
+                                       C.c_int, C.c_float, C.c_float, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_stream]),
+})
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
 

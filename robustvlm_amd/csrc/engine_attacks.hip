@@ -229,6 +229,73 @@ extern "C" int rvlm_pgd_run_tokens(rvlm_vit* h, const float* x, const float* del
                         iterations, stepsize, momentum, mode_max, x_adv_out, loss_trace, flags, (hipStream_t)stream);
 }
 
+// apgd (vlm_eval/attacks/apgd.py:163-368; L-inf and L2, mask = None, maximising) on the per-image token loss, every image of the batch
+// on its own: the loop of rvlm_apgd_run_norm below with the token step as the model and no classifier - `pred` is zero for every
+// image, as rvlm_apgd_masked_bookkeeping has it, so x_best_adv follows the last iterate (apgd.py:310).  Only the schedule (k,
+// size_decr, n_iter_min, counter3: data-independent) lives on the host; nothing is read back and nothing allocated.
+// Buffers: img_buf[0] x_adv, [1] x_adv_old, [2] x_best_adv, [3] grad, [4] grad_best; x_best is kept in the caller's x_best_out.
+extern "C" int rvlm_apgd_run_tokens(rvlm_vit* h, const float* x, const float* x_init, int B, int depth, int ln_post, int select,
+                                    const float* ref_tokens, int norm_kind, float eps, int n_iter, float step0, float rho,
+                                    float* x_best_out, float* loss_best_out, float* x_last_out, float* loss_trace_out,
+                                    float* step_out, int32_t* flags, rvlm_stream_t stream) {
+    RVLM_REQUIRE(h && x && x_best_out, "rvlm_apgd_run_tokens: null argument");
+    if (norm_kind != 0 && norm_kind != 2) return fail(RVLM_ERR_UNSUPPORTED, "rvlm_apgd_run_tokens: norm must be L-inf (0) or L2 (2)");
+    RVLM_REQUIRE(n_iter >= 1 && n_iter <= 1024, "rvlm_apgd_run_tokens: n_iter must be in 1..1024");
+    RVLM_REQUIRE(rho == rho, "rvlm_apgd_run_tokens: rho is NaN");
+    int rc = tokens_loop_check(h, B, depth, select, ref_tokens, RVLM_RED_NONE, "rvlm_apgd_run_tokens"); if (rc) return rc;
+    if (ln_post && (rc = tok_ensure(h, true))) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t npix = (size_t)3 * h->in_h * h->in_w, n = npix * B;
+    float *x_adv = h->img_buf[0], *x_adv_old = h->img_buf[1], *x_best_adv = h->img_buf[2], *grad = h->img_buf[3],
+          *grad_best = h->img_buf[4], *x_best = x_best_out;
+    // schedule (apgd.py:192-213)
+    int k = std::max((int)(0.22 * n_iter), 1);
+    const int n_iter_min = std::max((int)(0.06 * n_iter), 1), size_decr = std::max((int)(0.03 * n_iter), 1);
+    int counter3 = 0;
+    hipLaunchKernelGGL(clamp01_kernel, dim3(ew_blocks(n)), dim3(256), 0, s, x_init ? x_init : x, x_adv, n);
+    RVLM_CHECK_LAUNCH();
+    RVLM_HIP(hipMemcpyAsync(x_best, x_adv, n * 4, hipMemcpyDeviceToDevice, s));
+    RVLM_HIP(hipMemcpyAsync(x_best_adv, x_adv, n * 4, hipMemcpyDeviceToDevice, s));
+    RVLM_HIP(hipMemcpyAsync(x_adv_old, x_adv, n * 4, hipMemcpyDeviceToDevice, s));
+    RVLM_HIP(hipMemsetAsync(h->ap_loss_steps, 0, (size_t)n_iter * B * 4, s));
+    RVLM_HIP(hipMemsetAsync(h->ap_pred, 0, (size_t)B, s));          // no classifier: never "classified correctly"
+
+    auto eval = [&](bool need_grad) -> int {     // per-image loss into loss_ps; its seed 2 (t - ref) carries no 1 / B
+        return tokens_step(h, x_adv, nullptr, B, depth, ln_post != 0, select, ref_tokens, RVLM_RED_NONE, nullptr, nullptr, flags,
+                           need_grad ? grad : nullptr, s);
+    };
+    if ((rc = eval(true))) return rc;
+    RVLM_HIP(hipMemcpyAsync(grad_best, grad, n * 4, hipMemcpyDeviceToDevice, s));
+    if (loss_trace_out) RVLM_HIP(hipMemcpyAsync(loss_trace_out, h->loss_ps, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(init_apgd_state_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, B, h->loss_ps, h->ap_pred, step0,
+                       h->ap_loss_best, h->ap_loss_best_lc, h->ap_reduced_lc, h->ap_step, h->ap_acc);
+    RVLM_CHECK_LAUNCH();
+    for (int i = 0; i < n_iter; ++i) {
+        {
+            PROF("linf_update", 0, (double)n * 24);
+            if ((rc = apgd_step_pooled(norm_kind, x, x_adv, x_adv_old, grad, h->ap_step, i > 0 ? 0.75f : 1.0f, eps, npix, B, flags, s)))
+                return rc;
+        }
+        if ((rc = eval(i < n_iter - 1))) return rc;                 // apgd.py:300-304: the last iteration keeps the gradient it has
+        counter3 += 1;
+        const int do_check = counter3 == k;
+        if ((rc = rvlm_apgd_controller_rho(i, B, n_iter, k, do_check, rho, h->loss_ps, h->ap_pred, h->ap_loss_steps, h->ap_loss_best,
+                                           h->ap_loss_best_lc, h->ap_reduced_lc, h->ap_step, h->ap_acc, h->ap_f0, h->ap_f1, h->ap_f2,
+                                           s))) return rc;
+        {
+            PROF("linf_update", 0, (double)n * 8);
+            if ((rc = rvlm_apgd_select(x_adv, grad, x_best, grad_best, x_best_adv, h->ap_f0, h->ap_f1, h->ap_f2, npix, B, s))) return rc;
+        }
+        if (do_check) { counter3 = 0; k = std::max(k - size_decr, n_iter_min); }
+    }
+    if (loss_best_out) RVLM_HIP(hipMemcpyAsync(loss_best_out, h->ap_loss_best, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    if (x_last_out) RVLM_HIP(hipMemcpyAsync(x_last_out, x_best_adv, n * 4, hipMemcpyDeviceToDevice, s));
+    if (loss_trace_out)
+        RVLM_HIP(hipMemcpyAsync(loss_trace_out + B, h->ap_loss_steps, (size_t)n_iter * B * 4, hipMemcpyDeviceToDevice, s));
+    if (step_out) RVLM_HIP(hipMemcpyAsync(step_out, h->ap_step, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    return RVLM_OK;
+}
+
 extern "C" int rvlm_pgd_run(rvlm_vit* h, const float* x, const float* delta0, int B,
                             const rvlm_loss_spec* loss, float eps, int iterations, float stepsize,
                             float momentum, int mode_max, float* x_adv_out, float* loss_trace,

@@ -240,6 +240,9 @@ int vit_backward_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int 
 int vit_backward_params(rvlm_vit* h, const float* d_emb, int B, const ParamSink& sink, hipStream_t s);
 int vit_backward_params_tokens(rvlm_vit* h, const TokSeed& ts, const float* d_emb, int B, const ParamSink& sink, hipStream_t s);
 int vit_backward_from(rvlm_vit* hb, rvlm_vit* hx, const float* d_emb, int B, float* grad_x, hipStream_t s);
+// vlm_attack_kernels.hip: rvlm_apgd_linf_step (norm_kind 0) / rvlm_apgd_l2_step (2) with a flag word (RVLM_FLAG_NAN_GRAD) or null
+int apgd_step_pooled(int norm_kind, const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
+                     float eps, size_t n_per_sample, int B, int32_t* flags, hipStream_t stream);
 // grid of the element-wise kernels (grid-stride loops of 256 threads)
 static inline int ew_blocks(size_t n) { size_t b = (n + 1023) / 1024; if (b > 2048) b = 2048; if (b < 1) b = 1; return (int)b; }
 

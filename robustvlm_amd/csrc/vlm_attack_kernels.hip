@@ -424,28 +424,36 @@ extern "C" int rvlm_pgd_l2_update(const float* x, const float* grad, float* delt
     return RVLM_OK;
 }
 
+// The two pooled APGD steps with the flag word of the masked entry (RVLM_FLAG_NAN_GRAD): what the public entries below launch with
+// flags == NULL, and what the token APGD loop (engine_attacks.hip) launches with its own.  The flag word changes no output bit.
+namespace rvlm {
+int apgd_step_pooled(int norm_kind, const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
+                     float eps, size_t n_per_sample, int B, int32_t* flags, hipStream_t stream) {
+    const float oma = (float)(1.0 - (double)a);
+    if (norm_kind == 2)
+        hipLaunchKernelGGL(apgd_masked_l2_kernel<1>, dim3(B), dim3(1024), 0, stream, x, x_adv, x_adv_old, grad, nullptr, step, a, oma,
+                           eps, 1, n_per_sample, flags);
+    else if (n_per_sample % 4 == 0 && aligned16({x, x_adv, x_adv_old, grad}))
+        hipLaunchKernelGGL(apgd_masked_linf_kernel<4>, image_grid(n_per_sample, 4, B), dim3(256), 0, stream, x, x_adv, x_adv_old, grad,
+                           nullptr, step, a, oma, eps, 1, n_per_sample, flags);
+    else
+        hipLaunchKernelGGL(apgd_masked_linf_kernel<1>, image_grid(n_per_sample, 1, B), dim3(256), 0, stream, x, x_adv, x_adv_old, grad,
+                           nullptr, step, a, oma, eps, 1, n_per_sample, flags);
+    RVLM_CHECK_LAUNCH();
+    return RVLM_OK;
+}
+}  // namespace rvlm
+
 extern "C" int rvlm_apgd_l2_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
                                  float eps, size_t n_per_sample, int B, rvlm_stream_t stream) {
     RVLM_REQUIRE(x && x_adv && x_adv_old && grad && step && B > 0 && n_per_sample > 0, "rvlm_apgd_l2_step: bad args");
-    const float oma = (float)(1.0 - (double)a);
-    hipLaunchKernelGGL(apgd_masked_l2_kernel<1>, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, x_adv, x_adv_old, grad, nullptr,
-                       step, a, oma, eps, 1, n_per_sample, nullptr);
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
+    return apgd_step_pooled(2, x, x_adv, x_adv_old, grad, step, a, eps, n_per_sample, B, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int rvlm_apgd_linf_step(const float* x, float* x_adv, float* x_adv_old, const float* grad, const float* step, float a,
                                    float eps, size_t n_per_sample, int B, rvlm_stream_t stream) {
     RVLM_REQUIRE(x && x_adv && x_adv_old && grad && step && B > 0 && n_per_sample > 0, "rvlm_apgd_linf_step: bad args");
-    const float oma = (float)(1.0 - (double)a);
-    if (n_per_sample % 4 == 0 && aligned16({x, x_adv, x_adv_old, grad}))
-        hipLaunchKernelGGL(apgd_masked_linf_kernel<4>, image_grid(n_per_sample, 4, B), dim3(256), 0, (hipStream_t)stream, x, x_adv,
-                           x_adv_old, grad, nullptr, step, a, oma, eps, 1, n_per_sample, nullptr);
-    else
-        hipLaunchKernelGGL(apgd_masked_linf_kernel<1>, image_grid(n_per_sample, 1, B), dim3(256), 0, (hipStream_t)stream, x, x_adv,
-                           x_adv_old, grad, nullptr, step, a, oma, eps, 1, n_per_sample, nullptr);
-    RVLM_CHECK_LAUNCH();
-    return RVLM_OK;
+    return apgd_step_pooled(0, x, x_adv, x_adv_old, grad, step, a, eps, n_per_sample, B, nullptr, (hipStream_t)stream);
 }
 
 // apgd.py:321-351 against rvlm_apgd_controller_rho / rvlm_apgd_select (apgd_train.py:301-355), line by line: `y1 > loss_best`

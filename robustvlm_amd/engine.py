@@ -414,6 +414,35 @@ class VitEngine:
         self.generation += 1
         return out, flags, trace
 
+    def apgd_run_tokens(self, x, x_init, ref_tokens, eps, n_iter, step0, depth=None, ln_post=False, select="all", norm_kind=0,
+                        rho=0.75, want_trace=False, want_step=False):
+        """Whole apgd() loop (vlm_eval/attacks/apgd.py:163-368, maximising) on the device with the per-image token loss as the
+        model, every image on its own (rvlm_apgd_run_tokens).  ``x_init``: the start point (None: ``x``), clamped to [0, 1].
+        Returns (x_best, loss_best, x_last, flags, loss_trace [n_iter + 1, B] | None, step [B] | None)."""
+        h = self._token_handle("apgd_run_tokens")
+        self._check_images(x)
+        x = _f32c(x)
+        xi = None
+        if x_init is not None:
+            _require_cuda(x_init, "x_init")
+            xi = _f32c(x_init)
+            if xi.shape != x.shape or xi.device != x.device:
+                raise ValueError(f"x_init {tuple(xi.shape)} on {xi.device} does not match x {tuple(x.shape)} on {x.device}")
+        B = x.shape[0]
+        ref, sel = self._token_ref(ref_tokens, B, select)
+        x_best, x_last = torch.empty_like(x), torch.empty_like(x)
+        loss_best = torch.empty(B, dtype=torch.float32, device=x.device)
+        flags = torch.zeros(1, dtype=torch.int32, device=x.device)
+        trace = torch.zeros(max(int(n_iter), 0) + 1, B, dtype=torch.float32, device=x.device) if want_trace else None
+        step = torch.empty(B, dtype=torch.float32, device=x.device) if want_step else None
+        with torch.cuda.device(x.device):
+            L.check(self.lib.rvlm_apgd_run_tokens(h, x.data_ptr(), L.ptr(xi), B, self._depth(depth), int(bool(ln_post)), sel,
+                                                  ref.data_ptr(), int(norm_kind), float(eps), int(n_iter), float(step0), float(rho),
+                                                  x_best.data_ptr(), loss_best.data_ptr(), x_last.data_ptr(), L.ptr(trace),
+                                                  L.ptr(step), flags.data_ptr(), L.stream_ptr()), "rvlm_apgd_run_tokens")
+        self.generation += 1
+        return x_best, loss_best, x_last, flags, trace, step
+
     # ---- fused loops -----------------------------------------------------------------------------
     def _loss_spec(self, loss_kind, reduction, output_normalize, ref, targets, logit_scale, y_target=None, B=None):
         """The C loops take raw device pointers: everything the reference would catch with an assert / a shape error /

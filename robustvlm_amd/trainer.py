@@ -179,7 +179,8 @@ class AdversarialTrainer:
                 raise ValueError("inner_loss / loss_clean 'l2-tokens' go with loss='l2-tokens' (no joint pooled + token loss)")
             return None, token_select
         if attack == "apgd":
-            raise ValueError("loss='l2-tokens': attack 'apgd' not supported (no batched token APGD); use 'pgd' or 'none'")
+            raise ValueError("loss='l2-tokens': attack 'apgd' not supported as the training-time attack (the batched token APGD runs in "
+                             "eval_step_tokens only); use 'pgd' or 'none'")
         if attack not in ("pgd", "none"):
             raise ValueError(f"attack {attack} not supported")
         if attack != "none" and inner_loss != "l2-tokens":
@@ -353,6 +354,20 @@ class AdversarialTrainer:
         with torch.cuda.device(tokens.device):
             L.check(self.lib.rvlm_tokens_cosine(tokens.data_ptr(), ref.data_ptr(), B, S, W, sel, per.data_ptr(), mean.data_ptr(),
                                                 scratch.data_ptr(), L.stream_ptr()), "rvlm_tokens_cosine")
+        return mean.reshape(())
+
+    @torch.no_grad()
+    def _tokens_l2_mean(self, tokens, ref_tokens):
+        """mean_b sum (tokens - ref)^2 over the selected rows, the loss alone (rvlm_tokens_l2_loss_grad without a seed)."""
+        B, S, W = tokens.shape
+        ref, sel = self.engine._token_ref(ref_tokens, B, self.token_select)
+        per = torch.empty(B, dtype=torch.float32, device=tokens.device)
+        mean = torch.empty(1, dtype=torch.float32, device=tokens.device)
+        scratch = torch.empty(B * ((S + 7) // 8), dtype=torch.float32, device=tokens.device)
+        with torch.cuda.device(tokens.device):
+            L.check(self.lib.rvlm_tokens_l2_loss_grad(tokens.data_ptr(), ref.data_ptr(), B, S, W, sel, L.RED_MEAN, None, None, 0,
+                                                      per.data_ptr(), mean.data_ptr(), scratch.data_ptr(), None, L.stream_ptr()),
+                    "rvlm_tokens_l2_loss_grad")
         return mean.reshape(())
 
     def _train_step_tokens(self, data, data_adv, global_batch, global_metrics):
@@ -547,6 +562,39 @@ class AdversarialTrainer:
                     "eval/cos-sim": float(self._cos_mean(e_adv, e_cln))}
         self.model.train(was_training)
         return logs
+
+    def eval_step_tokens(self, data_eval, n_iter=50, pert_init=None):
+        """The token twin of ``eval_step`` (``loss="l2-tokens"`` only): the trained tower, in eval mode, under an ``n_iter``-step
+        batched APGD on the token loss it is trained on (rvlm_apgd_run_tokens; the trainer's ``norm`` / ``eps``; the iterate of
+        highest loss is the one evaluated), against the frozen copy's tokens at ``token_depth`` over ``token_select``.  Start: ``data_eval + pert_init``, or U(-eps, eps) drawn on
+        the device as ``_attack`` draws it - at the clean point itself the l2 gradient is exactly zero while the two towers agree.
+        Returns plain floats: 'eval/l2-tokens' (batch mean of the adversarial token loss against the frozen reference),
+        'eval/l2-tokens-clean' (the same on the clean images) and 'eval/cos-sim-tokens' (rvlm_tokens_cosine between the trained
+        model's adversarial and clean tokens).  Only forwards and input gradients run: parameters, gradients and optimizer state
+        are not touched, and the next ``train_step`` starts from forwards of its own."""
+        if not self.token_mode:
+            raise ValueError("eval_step_tokens evaluates the token loss: it needs loss='l2-tokens' (eval_step is the pooled one)")
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            with torch.no_grad():
+                eng, depth, sel = self.engine, self.token_depth, self.token_select
+                ref0 = self._select_rows(self.engine_orig.forward_tokens(data_eval, depth=depth)).contiguous()
+                if pert_init is None:
+                    pert_init = torch.zeros_like(data_eval).uniform_(-self.eps, self.eps)
+                x_best, loss_best, _, flags, _, _ = eng.apgd_run_tokens(
+                    data_eval, data_eval + pert_init, ref0, self.eps, n_iter, 2. * self.eps, depth=depth, ln_post=False, select=sel,
+                    norm_kind=0 if self.norm in LINF else 2)
+                tok_adv = eng.forward_tokens(x_best, depth=depth, save=False)
+                tok_cln = eng.forward_tokens(data_eval, depth=depth, save=False)
+                cos = self._tokens_cos_mean(tok_adv, self._select_rows(tok_cln).contiguous())
+                vals = torch.stack([loss_best.mean(), self._tokens_l2_mean(tok_cln, ref0), cos]).tolist()
+                flags = int(flags.item())
+            assert not (flags & L.FLAG_TOKENS_NONFINITE), "non-finite token loss"
+            _raise_from_flags(flags)
+        finally:
+            self.model.train(was_training)
+        return {"eval/l2-tokens": vals[0], "eval/l2-tokens-clean": vals[1], "eval/cos-sim-tokens": vals[2]}
 
     def state_dict(self):
         """open_clip ``visual.state_dict()`` of the fine-tuned tower (what …clip.py:239,470 saves).  Checkpoint time is also where
